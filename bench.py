@@ -6,7 +6,12 @@
 # HBM before the timed region starts; H2D is NOT in the timed region and
 # the PCIe-inclusive rate is reported in DESIGN.md).
 #
-#   python bench.py --gpus N --steps K --warmup W
+#   python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+#
+# A plain run sets up, warms up, times the K steps and prints the result
+# line. --dump-outputs DIR also writes what the last timed step computed
+# (DIR/C.npy, a fixed seeded column sample when C is large). --full adds
+# the legs that take runs of their own (the host-core CPU baseline).
 #
 # N > 1 is launched by the driver via torch.distributed.run (one rank per
 # GPU); ranks use gloo ONLY as the control plane (RCCL unique-id exchange,
@@ -64,6 +69,38 @@ def cpu_baseline_leg(args):
     }
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # per run, all ranks together (cap: 64 MB)
+
+
+def dump_outputs(eng, outdir, dC, rows, cols, pitch, fp32, rank, world):
+    """Write the C the last timed step left on the device: whole columns
+    of the col-major rows x cols image (pitch in elements). When C is
+    over budget, one seeded-random column per equal-width stratum, so
+    every column tile of the kernel is sampled and the choice is the
+    same from run to run. C_cols.npy holds the column indices."""
+    os.makedirs(outdir, exist_ok=True)
+    if rows == 0 or cols == 0:      # this rank owns an empty shard
+        return
+    dt = np.float32 if fp32 else np.float64
+    elem = 4 if fp32 else 8
+    ncols = int(min(cols, max(1, DUMP_BUDGET_BYTES // world // (rows * elem))))
+    if ncols == cols:
+        idx = np.arange(cols, dtype=np.int64)
+    else:
+        edges = np.linspace(0, cols, ncols + 1).astype(np.int64)
+        rng = np.random.default_rng(0xD0C5)
+        idx = edges[:-1] + (rng.random(ncols) * (edges[1:] - edges[:-1])
+                            ).astype(np.int64)
+    out = np.empty((rows, ncols), dtype=dt, order="F")
+    col = np.empty(rows, dtype=dt)
+    for j, cj in enumerate(idx):
+        eng.download_off(col, dC, int(cj) * pitch * elem, rows * elem)
+        out[:, j] = col
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(outdir, f"C{tag}.npy"), out)
+    np.save(os.path.join(outdir, f"C{tag}_cols.npy"), idx.astype(np.float64))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -88,6 +125,11 @@ def main():
                    default=env.get("MARLIN_BENCH_WORKLOAD", "gemm"))
     p.add_argument("--cpu-sample", type=int, default=12000)
     p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's C as DIR/C.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure "
+                        "(CPU baseline)")
     # run the SUMMA panel-loop path even at world 1 (1x1 grid, RCCL comm
     # of size 1): measures the distributed pipeline's overhead (panel
     # packs + beta-chained GEMMs) without xGMI traffic — the pre-SCALE
@@ -241,6 +283,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax[0])
 
+    if args.dump_outputs:
+        # C as a caller holds it: this rank's mi x nj col-major shard,
+        # pitch mip (the whole m x n at world 1); the epilogue's C is the
+        # transposed n x m image, pitch roundup(n, 128)
+        c_rows, c_cols, c_pitch = mi, nj, mip
+        if args.workload == "epilogue" and world == 1 and not args.force_summa:
+            c_rows, c_cols, c_pitch = n, m, njp
+        dump_outputs(eng, args.dump_outputs, dC, c_rows, c_cols, c_pitch,
+                     fp32, rank, world)
+
     if rank == 0:
         flops = 2.0 * m * k * n * args.steps
         tf = flops / dt / 1e12
@@ -319,7 +371,7 @@ def main():
             },
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_leg(args)
         print(json.dumps(out), flush=True)
     if dist:

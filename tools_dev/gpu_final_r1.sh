@@ -10,7 +10,7 @@ cd $R
 ./marlinx bench 8192 8192 8192 2 1 >> gpurun_out/marlinx.log 2>&1
 
 # the driver-contract default bench (incl. cpu_baseline leg)
-timeout 500 python bench.py > gpurun_out/bench_final.log 2>&1
+timeout 500 python bench.py --full > "${LOGDIR:-.}/bench_final.log" 2>&1
 
 cd /tmp && export TMPDIR=/tmp
 B20="python $R/bench.py --gpus 1 --warmup 1 --no-cpu-baseline"

@@ -21,7 +21,7 @@ python -c 'import __graft_entry__; __graft_entry__.smoke()' \
   > gpurun_out/r2_smoke.log 2>&1
 
 # headline bench (driver-contract form, short)
-timeout 500 python bench.py --steps 3 --warmup 1 \
+timeout 500 python bench.py --steps 3 --warmup 1 --full \
   > gpurun_out/r2_bench20000.log 2>&1
 # epilogue leg (config 5 fused (A*B)^T + D, device-resident)
 timeout 500 python bench.py --workload epilogue --steps 3 --warmup 1 \

@@ -34,7 +34,7 @@ timeout 400 $B --steps 3 > gpurun_out/r2c5_f64_base.log 2>&1
 MARLIN_GEMM_PHASE=8 timeout 400 $B --steps 3 > gpurun_out/r2c5_f64_ph8.log 2>&1
 
 # driver-form default bench (incl. cpu_baseline) + CLI verify
-timeout 500 python bench.py > gpurun_out/r2c5_bench_default.log 2>&1
+timeout 500 python bench.py --full > "${LOGDIR:-.}/r2c5_bench_default.log" 2>&1
 ./marlinx verify 300 200 100 > gpurun_out/r2c5_cli.log 2>&1
 ./marlinx bench 8192 8192 8192 2 1 >> gpurun_out/r2c5_cli.log 2>&1
 
