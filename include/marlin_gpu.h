@@ -156,7 +156,19 @@ int mx_download(mx_ctx* ctx, void* dst, const mx_dbuf* src, int64_t bytes);
 int mx_fill_random(mx_ctx* ctx, mx_dbuf* buf, int64_t n_elems,
                    uint64_t seed, int is_fp32);
 /* Device-resident GEMM on padded-pitch device buffers created by the
- * helpers above. lda/ldb/ldc are element pitches. */
+ * helpers above. lda/ldb/ldc are element pitches.
+ *
+ * Pitch contract of every device GEMM entry (checked before any launch;
+ * a violation returns MX_EINVAL and touches no buffer):
+ *   - m and n are multiples of 128, k of 16 (the caller pads with zeros);
+ *   - lda >= m, ldb >= k, ldc >= m (fused epilogue: ldc >= n, C is n x m);
+ *   - every pitch is a multiple of 16 bytes, i.e. of 2 fp64 / 4 fp32
+ *     elements: the kernels move 16-byte chunks (global_load_lds, float4
+ *     epilogue stores), so each column start must stay 16-byte aligned;
+ *   - rows [m, ldc) of C are never read or written.
+ * m == 0 or n == 0 is a no-op and k == 0 means C = 0 (unchanged when
+ * accumulating) on the plain entries; the fused epilogue entry has no
+ * empty-shape no-op and rejects m, n or k <= 0. */
 int mx_dgemm_device(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
                     const mx_dbuf* dA, int64_t lda,
                     const mx_dbuf* dB, int64_t ldb,
@@ -178,6 +190,23 @@ int mx_gemm_device_ex(mx_ctx* ctx, int is_fp32, int beta_one, int64_t m,
                       int64_t k, int64_t n, const mx_dbuf* dA, int64_t lda,
                       const mx_dbuf* dB, int64_t ldb, mx_dbuf* dC,
                       int64_t ldc);
+
+/* Introspection: the gemm_mfma_kernel instantiation and remap arguments
+ * of the most recent plain GEMM launch in this process (any entry that
+ * reaches the kernel launcher; all zero before the first launch). The
+ * MARLIN_GEMM_CFG / _REMAP / _BAND / _PHASE knobs are latched per
+ * process and fall back silently when a shape does not divide, so this
+ * is how a test proves which variant it ran. */
+typedef struct {
+  int is_fp32;     /* 0 = fp64, 1 = fp32                                   */
+  int beta_one;    /* 1 = accumulating instantiation (C += A*B)            */
+  int bk;          /* k-step: 16 or 32                                     */
+  int bm;          /* block tile rows: 128 or 256                          */
+  int waves;       /* waves per block: 4 (2x2) or 8 (2x4, 4x2)             */
+  int band;        /* block-column band width; < 0 = plain band order      */
+  int phase_mask;  /* k-phase stagger mask, 0 = off                        */
+} mx_gemm_cfg_t;
+int mx_last_gemm_config(mx_ctx* ctx, mx_gemm_cfg_t* out);
 
 /* SUMMA on device-resident local shards (bench hot loop: inputs already
  * in HBM when the timed region starts). Shard pitches are the PADDED

@@ -26,6 +26,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "../../include/marlin_gpu.h"   // mx_gemm_cfg_t
+
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -520,17 +522,8 @@ __global__ void zero_pad_kernel(T* __restrict__ buf, int64_t rows_total,
 // (BlockMatrix.scala:344-507: add/subtract matrix+scalar, subtractBy,
 // divide, divideBy, dotProduct=element-wise multiply; DenseVecMatrix
 // multiply(scalar)). HBM-bound map kernels; layout-agnostic (flat).
-enum MxMapOp {
-    MX_OP_ADD = 0,    // C = A + B
-    MX_OP_SUB = 1,    // C = A - B
-    MX_OP_EMUL = 2,   // C = A .* B   (reference "dotProduct")
-    MX_OP_ADDS = 3,   // C = A + s
-    MX_OP_SUBS = 4,   // C = A - s
-    MX_OP_RSUBS = 5,  // C = s - A    (subtractBy)
-    MX_OP_MULS = 6,   // C = A * s
-    MX_OP_DIVS = 7,   // C = A / s
-    MX_OP_RDIVS = 8,  // C = s / A    (divideBy)
-};
+// Op codes: MX_OP_* of include/marlin_gpu.h (ADD/SUB/EMUL binary, then
+// ADDS, SUBS, RSUBS = s - A, MULS, DIVS, RDIVS = s / A).
 
 template <typename T>
 __global__ void map_kernel(int op, int64_t n, const T* __restrict__ a,
@@ -667,12 +660,32 @@ __global__ void gemv_reduce_kernel(int64_t m, int nchunks,
 // C-visible launchers (called from marlin_gpu.cpp).
 extern "C" {
 
+// What mxk_gemm last launched (mx_last_gemm_config): the env knobs below
+// are latched per process, so a test can only prove which instantiation
+// it exercised by reading this record back.
+static mx_gemm_cfg_t g_last_gemm_cfg = {};
+
+void mxk_last_gemm_config(mx_gemm_cfg_t* out) { *out = g_last_gemm_cfg; }
+
+// Pitch contract of the GEMM kernels: every column start must stay
+// 16-byte aligned (global_load_lds moves 16-byte chunks; the fused
+// epilogue stores float4), and a pitch must cover its leading dimension.
+static inline bool pitch_ok(int64_t ld, int64_t rows, int64_t elems16) {
+    return ld >= rows && ld % elems16 == 0;
+}
+
 int mxk_gemm(int is_fp32, int beta_one,
              int64_t M, int64_t N, int64_t K,
              const void* A, int64_t lda, const void* B, int64_t ldb,
              void* C, int64_t ldc, hipStream_t stream) {
     if (M < 0 || N < 0 || K < 0) return -4;
     if (M == 0 || N == 0) return 0;            // empty tile: nothing to do
+    {
+        const int64_t e16 = is_fp32 ? 4 : 2;   // elements per 16 bytes
+        if (!pitch_ok(lda, M, e16) || !pitch_ok(ldb, K, e16) ||
+            !pitch_ok(ldc, M, e16))
+            return -4;
+    }
     if (K == 0) {                              // C = 0 (or unchanged if +=)
         if (!beta_one) {
             size_t es = is_fp32 ? 4 : 8;
@@ -702,10 +715,14 @@ int mxk_gemm(int is_fp32, int beta_one,
     static const char* phenv = getenv("MARLIN_GEMM_PHASE");
     int phase_mask = phenv ? atoi(phenv) : 0;
     #define LAUNCH(TY, BETA, BK, BMv, WMv, WNv)                            \
+        do {                                                               \
+        g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(TY) == 4, BETA, BK, BMv,    \
+                                        WMv * WNv, band, phase_mask};      \
         hipLaunchKernelGGL((gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv>),\
             dim3((unsigned)((M / BMv) * nbn)), dim3(WMv * WNv * 64), 0,    \
             stream, M, N, K, (const TY*)A, lda, (const TY*)B, ldb, (TY*)C, \
-            ldc, (int)(M / BMv), band, phase_mask)
+            ldc, (int)(M / BMv), band, phase_mask);                        \
+        } while (0)
     if (is_fp32) {
         if (beta_one) { if (bk32) LAUNCH(float, 1, 32, 128, 2, 4); else LAUNCH(float, 1, 16, 128, 2, 2); }
         else          { if (bk32) LAUNCH(float, 0, 32, 128, 2, 4); else LAUNCH(float, 0, 16, 128, 2, 2); }
@@ -725,7 +742,13 @@ int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K,
                           const float* B, int64_t ldb,
                           float* C, int64_t ldc, const float* addC,
                           hipStream_t stream) {
+    // no empty-shape no-op here: the kernel prefetches k-tile 0
+    // unconditionally and a zero-block grid is a launch error
+    if (M <= 0 || N <= 0 || K <= 0) return -4;
     if (M % 128 || N % 128 || K % 16) return -4;
+    // C/addC are N x M: float4 rows need ldc % 4 == 0 and ldc >= N
+    if (!pitch_ok(lda, M, 4) || !pitch_ok(ldb, K, 4) || !pitch_ok(ldc, N, 4))
+        return -4;
     int nbm = (int)(M / 128), nbn = (int)(N / 128);
     int band = nbn < 8 ? nbn : 8;
     dim3 grid((unsigned)(nbm * nbn)), block(256);

@@ -47,6 +47,7 @@ int mxk_transpose(int is_fp32, int64_t m, int64_t n, const void* in,
                   void* out, hipStream_t stream);
 int mxk_gemv(int is_fp32, int64_t m, int64_t n, int64_t lda, const void* A,
              const void* x, double* partial, void* y, hipStream_t stream);
+void mxk_last_gemm_config(mx_gemm_cfg_t* out);
 }
 
 #define HIP_OK(x)                                                        \
@@ -424,6 +425,12 @@ int mx_gemm_device_ex(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
   c->st.flops = 2.0 * m * k * n;
   return gemm_device(c, is_fp32, beta_one, m, k, n, dA->ptr, lda, dB->ptr,
                      ldb, dC->ptr, ldc);
+}
+
+int mx_last_gemm_config(mx_ctx* c, mx_gemm_cfg_t* out) {
+  if (!c || !out) return MX_EINVAL;
+  mxk_last_gemm_config(out);
+  return MX_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -38,6 +38,11 @@ class MxStats(ctypes.Structure):
     ]
 
 
+class MxGemmCfg(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int) for f in (
+        "is_fp32", "beta_one", "bk", "bm", "waves", "band", "phase_mask")]
+
+
 def _load():
     if not os.path.exists(_SO):
         raise EngineUnavailable(
@@ -121,6 +126,7 @@ def _load():
         "mx_dgemv_device": (ctypes.c_int, [vp, i64, i64, vp, i64, P(dbl),
                                            P(dbl)]),
         "mx_stats": (ctypes.c_int, [vp, P(MxStats)]),
+        "mx_last_gemm_config": (ctypes.c_int, [vp, P(MxGemmCfg)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -461,6 +467,14 @@ class Engine:
         st = MxStats()
         _ck(lib().mx_stats(self._ctx, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in MxStats._fields_}
+
+    def last_gemm_config(self):
+        """Instantiation + remap arguments of the last plain GEMM launch
+        (is_fp32, beta_one, bk, bm, waves, band, phase_mask)."""
+        cfg = MxGemmCfg()
+        _ck(lib().mx_last_gemm_config(self._ctx, ctypes.byref(cfg)),
+            "mx_last_gemm_config")
+        return {f: getattr(cfg, f) for f, _ in MxGemmCfg._fields_}
 
     # -- device-resident matrices (RDD.cache() analog) ----------------------
     def upload_matrix(self, a, fp32=False):

@@ -3,10 +3,14 @@
 # addition/subtract ...", :319-324 "sum", :326-338 "dot product",
 # :302-316 transpose), restated as data, run through the engine's
 # mx_map/mx_sum/mx_transpose via the operator mirror.
+import ctypes
+import math
+
 import numpy as np
 import pytest
 
 from marlin_amd import Engine, DenseVecMatrix
+from marlin_amd import engine as E
 from oracle import gen_matrix
 
 pytestmark = pytest.mark.gpu
@@ -97,3 +101,89 @@ def test_elementwise_large_random(eng):
 def test_dimension_mismatch(eng):
     with pytest.raises(ValueError):
         dvm(eng).add(DenseVecMatrix(np.ones((3, 4)), engine=eng))
+
+
+# ---------------------------------------------------------------------------
+# fp32 instantiations of map/sum/transpose (the engine wrappers always
+# pass is_fp32=0, so these go through the C ABI directly) and the scalar
+# ops at a size where the grid-stride loops run: 1000x700 = 700000
+# elements > the 2048x256 = 524288-thread map grid and the 1024x256 =
+# 262144-thread sum grid.
+BIG = (1000, 700)
+
+
+def _vp(x):
+    return x.ctypes.data_as(ctypes.c_void_p)
+
+
+def _map32(eng, op, a, b=None, scalar=0.0):
+    c = np.empty_like(a)
+    rc = E.lib().mx_map(eng._ctx, Engine.OPS[op], 1, a.size, _vp(a),
+                        _vp(b) if b is not None else None, float(scalar),
+                        _vp(c))
+    assert rc == 0, rc
+    return c
+
+
+def test_map_fp32_all_ops_bitexact(eng):
+    # inputs in [0.5, 1.5): bounded away from 0 for rdivs, no subnormal
+    # results. Every op is ONE IEEE-754 binary32 operation on the scalar
+    # cast to float32 first (as map_kernel does), so numpy's float32
+    # result is the exact expectation.
+    a = gen_matrix(*BIG, seed=11, dtype=np.float32) + np.float32(0.5)
+    b = gen_matrix(*BIG, seed=12, dtype=np.float32) + np.float32(0.5)
+    assert a.dtype == np.float32 and a.min() >= 0.5
+    s64 = 3.3                        # not representable in float32
+    s = np.float32(s64)
+    expect = {
+        "add": a + b, "sub": a - b, "emul": a * b,
+        "adds": a + s, "subs": a - s, "rsubs": s - a,
+        "muls": a * s, "divs": a / s, "rdivs": s / a,
+    }
+    assert set(expect) == set(Engine.OPS)
+    for op, ref in expect.items():
+        assert ref.dtype == np.float32
+        got = _map32(eng, op, a, b if Engine.OPS[op] <= 2 else None, s64)
+        np.testing.assert_array_equal(got.view(np.uint32),
+                                      ref.view(np.uint32), err_msg=op)
+
+
+def test_map_fp64_scalar_ops_large(eng):
+    # adds/subs/rsubs/divs were only ever checked on a 4x4 matrix
+    a = gen_matrix(*BIG, seed=13) + 0.5
+    s = 3.3
+    np.testing.assert_array_equal(eng.map_op("adds", a, scalar=s), a + s)
+    np.testing.assert_array_equal(eng.map_op("subs", a, scalar=s), a - s)
+    np.testing.assert_array_equal(eng.map_op("rsubs", a, scalar=s), s - a)
+    np.testing.assert_array_equal(eng.map_op("divs", a, scalar=s), a / s)
+
+
+def test_sum_fp32_accumulates_in_double(eng):
+    # sum_stage1_kernel<float> widens each element to double (exact) and
+    # adds in double; stage 2 adds the partials in double. Any summation
+    # order of n terms with unit roundoff u = 2^-53 obeys
+    #   |fl(sum) - sum| <= gamma_{n-1} * sum|a_i|,
+    #   gamma_{n-1} = (n-1)u / (1 - (n-1)u) <= n*u   (as n(n-1)u <= 1),
+    # so the bound is n * 2^-53 * sum|a|, against the correctly rounded
+    # math.fsum of the same float32 values. Mixed signs make sum|a| the
+    # honest scale (the sum itself nearly cancels).
+    a = gen_matrix(*BIG, seed=14, dtype=np.float32) - np.float32(0.5)
+    n = a.size
+    assert n * (n - 1) * 2.0 ** -53 <= 1
+    out = ctypes.c_double()
+    rc = E.lib().mx_sum(eng._ctx, 1, n, _vp(a), ctypes.byref(out))
+    assert rc == 0, rc
+    vals = a.ravel(order="F").astype(np.float64)
+    exact = math.fsum(vals.tolist())
+    bound = n * 2.0 ** -53 * math.fsum(np.abs(vals).tolist())
+    assert abs(out.value - exact) <= bound, (out.value, exact, bound)
+
+
+@pytest.mark.parametrize("shape", [(517, 301), (33, 1)])
+def test_transpose_fp32(eng, shape):
+    m, n = shape
+    a = gen_matrix(m, n, seed=15, dtype=np.float32)
+    c = np.full((n, m), np.nan, dtype=np.float32, order="F")
+    rc = E.lib().mx_transpose(eng._ctx, 1, m, n, _vp(a), _vp(c))
+    assert rc == 0, rc
+    np.testing.assert_array_equal(c, a.T)
