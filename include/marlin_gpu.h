@@ -208,6 +208,15 @@ typedef struct {
 } mx_gemm_cfg_t;
 int mx_last_gemm_config(mx_ctx* ctx, mx_gemm_cfg_t* out);
 
+/* The k-loop of that same launch: 1 = pipelined across tiles (one
+ * barrier per k-step; the default of every variant but fp32 at bk 16),
+ * 0 = two-barrier loop. The latched MARLIN_GEMM_LOOP=twobar / =pipe
+ * knob forces one loop for every variant; a pitch of 2^26 elements or
+ * more, which the pipelined loop's 32-bit lane offsets do not cover,
+ * always takes the two-barrier loop. 0 before the first launch. Both
+ * loops give bit-identical results. */
+int mx_last_gemm_loop(mx_ctx* ctx, int* out);
+
 /* SUMMA on device-resident local shards (bench hot loop: inputs already
  * in HBM when the timed region starts). Shard pitches are the PADDED
  * sizes: A_local pitch roundup(my_m,128) x my_ka cols; B_local pitch

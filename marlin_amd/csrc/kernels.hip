@@ -12,8 +12,13 @@
 //   - 128x128 block tile, BK=16 K-step, 256 threads = 4 waves in a 2x2
 //     wave grid, each wave owns a 64x64 sub-tile = 4x4 MFMA fragments.
 //   - A/B staged through LDS with 16-byte global_load_lds (direct HBM->LDS
-//     DMA), double-buffered: raw s_barrier + counted vmcnt keeps the next
-//     tile's DMA in flight across the barrier.
+//     DMA), double-buffered, the next tile's DMA always a full k-step
+//     ahead. The k-loop is software-pipelined across tiles: ONE raw
+//     s_barrier per k-step, placed before the last quad's MFMAs, which
+//     cover the next DMA issue and the next tile's first fragment reads;
+//     DMA addresses are running wave-uniform pointers + constant lane
+//     offsets. The earlier two-barrier loop stays selectable
+//     (MARLIN_GEMM_LOOP=twobar) and is still fp32/BK=16's default.
 //   - All matrices COLUMN-MAJOR with padded leading dims (multiples of the
 //     tile) — the host pads, so the kernel has no edge paths.
 //   - Grid is remapped into column bands so the ~512 resident blocks share
@@ -25,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "../../include/marlin_gpu.h"   // mx_gemm_cfg_t
 
@@ -71,8 +78,21 @@ DEVFN void glds16(const void* g, void* lds) {
 // 2 waves/SIMD. Alternates kept for re-evaluation behind MARLIN_GEMM_CFG:
 // bk32 (512-thread, half barrier rate, 58.6 TF) and bm256 (256x128 tile,
 // half DMA-per-flop, 63.6 TF) — both measured slower than the default's
-// 67.9 TF at 20000^3.
-template <typename T, int BETA, int BK, int BM, int WM, int WN>
+// 67.9 TF at 20000^3 with the two-barrier loop. With the pipelined loop
+// the default reaches 70.4 and bk32 62.6 at 20000^3, and at 20480^3 (the
+// nearest size a 256-row tile divides) the default 71.4 vs bm256 70.2:
+// the ranking holds (profiles/r03_pipelined_loop.md).
+//
+// PIPE selects the k-loop (both accumulate in the same order, so their
+// results are bit-identical):
+//   0  two barriers per k-step, DMA addresses rebuilt from kt each step
+//      (MARLIN_GEMM_LOOP=twobar);
+//   1  software-pipelined across tiles: one barrier per k-step, placed
+//      ahead of the last quad's MFMAs, which cover the next-but-one
+//      tile's DMA issue and the next tile's quad-0 fragment reads; DMA
+//      sources are wave-uniform running pointers plus loop-invariant
+//      32-bit lane offsets (see the comment above that loop).
+template <typename T, int BETA, int BK, int BM, int WM, int WN, int PIPE>
 __launch_bounds__(WM * WN * 64, 2)
 __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                                  const T* __restrict__ A, int64_t lda,
@@ -236,6 +256,48 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // blocks sharing a CU do not hit their DMA-wait/barrier windows in
     // sync. Default off (phase_mask 0 = ascending k, reference order).
     const int ph = (phase_mask && (id & phase_mask)) ? (ntiles >> 1) : 0;
+
+    // Pipelined loop's halves of a quad (the two-barrier loop below keeps
+    // its own inline copy so that its code stays what it was): fragments
+    // of quad q (k = 4q .. 4q+3) of the tile staged at At/Bt, undoing the
+    // DMA-side swizzles; then the quad's MT x NT MFMAs.
+    auto read_quad = [&](const T* At, const T* Bt, int q, T (&a)[MT],
+                         T (&b)[NT]) {
+        const int kk = q * 4 + l4;
+        #pragma unroll
+        for (int mt = 0; mt < MT; mt++) {
+            int rr = wm * (MT * 16) + mt * 16 + l15;
+            if constexpr (E == 2)
+                a[mt] = At[kk * BM + (((rr >> 1) ^ ((kk & 1) << 3)) << 1)
+                           + (rr & 1)];
+            else
+                a[mt] = At[kk * BM + (((rr >> 2) ^ ((kk & 1) << 2)) << 2)
+                           + (rr & 3)];
+        }
+        #pragma unroll
+        for (int nt = 0; nt < NT; nt++) {
+            int cb = wn * (NT * 16) + nt * 16 + l15;
+            if constexpr (E == 2)
+                b[nt] = Bt[cb * BK
+                           + ((((kk >> 1) ^ ((cb >> BSH) & BMASK)) << 1))
+                           + (kk & 1)];
+            else if constexpr (E == 4 && BK == 16)
+                b[nt] = Bt[cb * BK
+                           + (((kk >> 2) ^ ((cb >> 1) & 3)) << 2)
+                           + (kk & 3)];
+            else
+                b[nt] = Bt[cb * BK + kk];
+        }
+    };
+    auto mfma_quad = [&](const T (&a)[MT], const T (&b)[NT]) {
+        #pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+            #pragma unroll
+            for (int nt = 0; nt < NT; nt++)
+                acc[mt][nt] = mfma_16x16x4(a[mt], b[nt], acc[mt][nt]);
+    };
+
+    if constexpr (!PIPE) {
     issue_tile(ph, 0);
 
     // Two barriers per k-step with the next tile's DMA issued EARLY and
@@ -303,6 +365,157 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();        // readers done before overwrite
+    }
+    } else {
+    // Pipelined loop: every wave hides its own loop-top work. Step s
+    // (tile s in buffer s & 1) runs
+    //     quads 0 .. Q-2:  read quad q+1's fragments, MFMAs of quad q
+    //     lgkmcnt(0)       quad Q-1's fragments are in registers: this
+    //                      wave has finished reading tile s
+    //     vmcnt(0)         this wave's pieces of tile s+1 (issued a full
+    //                      step ago, the only DMAs outstanding) landed
+    //     s_barrier        tile s+1 visible AND tile s's buffer free
+    //     read quad 0 of tile s+1; issue tile s+2 into tile s's buffer
+    //     MFMAs of quad Q-1 of tile s, with the line above interleaved
+    //     behind them (one read, then one DMA piece, per MFMA)
+    // so the DMA lead stays one full step and the one barrier does both
+    // jobs of the two-barrier loop. The last two steps are peeled (no
+    // tile left to issue / to read), which keeps the steady-state body
+    // one branch-free block the scheduler hints can order.
+    //
+    // DMA sources: (wave-uniform running pointer + uniform per-piece
+    // offset) + per-lane 32-bit byte offset. The lane offsets hold the
+    // XOR swizzle and are loop-invariant; the pointers advance by one
+    // tile per issue and are reset where the MARLIN_GEMM_PHASE rotation
+    // wraps. The launcher guarantees the lane offsets fit 32 bits.
+    constexpr int Q = BK / 4;
+    constexpr int P = A_GLDS + B_GLDS;       // DMA pieces per wave and tile
+    static_assert(Q % 2 == 0, "fragment registers ping-pong per quad");
+    const int swid = __builtin_amdgcn_readfirstlane(wid);
+
+    uint32_t a_lane[A_GLDS], b_lane[B_GLDS];     // per-lane byte offsets
+    int64_t a_uni[A_GLDS], b_uni[B_GLDS];        // per-piece uniform offsets
+    int a_lds[A_GLDS], b_lds[B_GLDS];            // LDS element offsets, buf 0
+    #pragma unroll
+    for (int i = 0; i < A_GLDS; i++) {
+        if constexpr (BM * sizeof(T) >= 1024) {
+            constexpr int CPC = BM * sizeof(T) / 1024;
+            int q = swid * A_GLDS + i;
+            int c = q / CPC, half = q - (q / CPC) * CPC;
+            int lane_row;
+            if constexpr (E == 2)
+                lane_row = (half * 64 + (lane ^ ((c & 1) << 3))) * E;
+            else
+                lane_row = (half * (1024 / sizeof(T) / E) * E)
+                           + ((lane ^ ((c & 1) << 2)) * E);
+            a_lane[i] = (uint32_t)lane_row * (uint32_t)sizeof(T);
+            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
+            a_lds[i] = c * BM + half * (int)(1024 / sizeof(T));
+        } else {
+            int c = (swid * A_GLDS + i) * A_COLS_PER_GLDS;
+            int lane_col = lane / (BM / E);        // 0 or extra col
+            int lane_row;
+            if constexpr (E == 2)
+                lane_row = (lane ^ (((c + lane_col) & 1) << 3)) * E;
+            else  // f32: 16B chunk XOR 4 by k parity (banks mod 32)
+                lane_row = ((lane % (BM / E)) ^ (((c + lane_col) & 1) << 2)) * E;
+            a_lane[i] = ((uint32_t)lane_col * (uint32_t)lda
+                         + (uint32_t)lane_row) * (uint32_t)sizeof(T);
+            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
+            a_lds[i] = c * BM;
+        }
+    }
+    #pragma unroll
+    for (int i = 0; i < B_GLDS; i++) {
+        int c = (swid * B_GLDS + i) * B_COLS_PER_GLDS;
+        int lane_col = lane / (BK / E);
+        int lane_row;
+        if constexpr (E == 2)
+            lane_row = ((lane % (BK / E)) ^ (((c + lane_col) >> BSH) & BMASK)) * E;
+        else if constexpr (E == 4 && BK == 16)
+            lane_row = ((lane % 4) ^ (((c + lane_col) >> 1) & 3)) * E;
+        else
+            lane_row = (lane % (BK / E)) * E;
+        b_lane[i] = ((uint32_t)lane_col * (uint32_t)ldb
+                     + (uint32_t)lane_row) * (uint32_t)sizeof(T);
+        b_uni[i] = (int64_t)c * ldb * (int64_t)sizeof(T);
+        b_lds[i] = c * BK;
+    }
+
+    const char* const pA0 = (const char*)(A + row0);           // tile 0
+    const char* const pB0 = (const char*)(B + col0 * ldb);
+    const int64_t stepA = (int64_t)BK * lda * (int64_t)sizeof(T);
+    constexpr int64_t stepB = (int64_t)BK * sizeof(T);
+    const char* pA = pA0 + ph * stepA;       // tile the next issue loads
+    const char* pB = pB0 + ph * stepB;
+    int kt = ph;
+    auto issue_next = [&](int buf) {
+        #pragma unroll
+        for (int i = 0; i < A_GLDS; i++)
+            glds16(pA + a_uni[i] + a_lane[i], &As[buf * BK * BM + a_lds[i]]);
+        #pragma unroll
+        for (int i = 0; i < B_GLDS; i++)
+            glds16(pB + b_uni[i] + b_lane[i], &Bs[buf * BN * BK + b_lds[i]]);
+        kt++; pA += stepA; pB += stepB;
+        if (kt == ntiles) { kt = 0; pA = pA0; pB = pB0; }      // phase wrap
+    };
+
+    T fa[2][MT], fb[2][NT];                  // fragments of quad q in [q & 1]
+    issue_next(0);
+    if (ntiles > 1) {
+        issue_next(1);
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(P) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();            // tile 0 visible
+    read_quad(As, Bs, 0, fa[0], fb[0]);
+
+    // AHEAD: tiles that follow tile s; 2 or more = steady state
+    auto step = [&](int s, auto ahead) {
+        constexpr int AHEAD = decltype(ahead)::value;
+        const int buf = s & 1;
+        const T* At = &As[buf * BK * BM];
+        const T* Bt = &Bs[buf * BN * BK];
+        #pragma unroll
+        for (int q = 0; q + 1 < Q; q++) {
+            read_quad(At, Bt, q + 1, fa[(q + 1) & 1], fb[(q + 1) & 1]);
+            mfma_quad(fa[q & 1], fb[q & 1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if constexpr (AHEAD >= 1) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            // reads first: the compiler keeps LDS reads and DMA writes in
+            // source order, and the fragments are needed sooner
+            read_quad(&As[(buf ^ 1) * BK * BM], &Bs[(buf ^ 1) * BN * BK], 0,
+                      fa[0], fb[0]);
+            if constexpr (AHEAD >= 2) issue_next(buf);
+        }
+        mfma_quad(fa[1], fb[1]);             // quad Q-1 of tile s
+        if constexpr (AHEAD >= 1) {
+            // one fragment read, then one DMA piece, behind each MFMA
+            #pragma unroll
+            for (int g = 0; g < MT + NT; g++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+            }
+            if constexpr (AHEAD >= 2) {
+                #pragma unroll
+                for (int g = 0; g < P; g++) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // VMEM (DMA)
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int s = 0;
+    for (; s + 2 < ntiles; s++) step(s, std::integral_constant<int, 2>{});
+    if (s + 1 < ntiles) { step(s, std::integral_constant<int, 1>{}); s++; }
+    step(s, std::integral_constant<int, 0>{});
     }
 
     // --- epilogue (row map per type, see above) --------------------------
@@ -667,6 +880,11 @@ static mx_gemm_cfg_t g_last_gemm_cfg = {};
 
 void mxk_last_gemm_config(mx_gemm_cfg_t* out) { *out = g_last_gemm_cfg; }
 
+// k-loop of that launch (mx_last_gemm_loop): 0 = two-barrier, 1 = pipelined
+static int g_last_gemm_loop = 0;
+
+void mxk_last_gemm_loop(int* out) { *out = g_last_gemm_loop; }
+
 // Pitch contract of the GEMM kernels: every column start must stay
 // 16-byte aligned (global_load_lds moves 16-byte chunks; the fused
 // epilogue stores float4), and a pitch must cover its leading dimension.
@@ -714,14 +932,35 @@ int mxk_gemm(int is_fp32, int beta_one,
     // k-phase stagger mask (experiment; see kernel comment). 0 = off.
     static const char* phenv = getenv("MARLIN_GEMM_PHASE");
     int phase_mask = phenv ? atoi(phenv) : 0;
+    // k-loop, decided per variant by paired runs on one box
+    // (profiles/r03_pipelined_loop.md): the pipelined one-barrier loop
+    // won for every fp64 variant (+6.5% default, +6.2% bk32, +9.9%
+    // bm256) and for fp32 bk32 (+7.2%), and lost for fp32 BK=16 (-3.0%;
+    // presumably its 4 waves/SIMD already cover the loop top), which
+    // keeps the two-barrier loop. MARLIN_GEMM_LOOP=twobar / =pipe force
+    // one loop everywhere (paired comparisons, tests). A pitch so large
+    // that the pipelined loop's 32-bit per-lane DMA offsets (up to 15
+    // columns of B, 1 of A, plus one 1 KiB run) could overflow always
+    // takes the two-barrier loop.
+    static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
+    const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
+                      : loopenv[0] == 'p' ? 1 : -1;
+    const bool pitch32 = lda < ((int64_t)1 << 26) && ldb < ((int64_t)1 << 26);
+    #define LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, PIPE)                 \
+        hipLaunchKernelGGL(                                                \
+            (gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv, PIPE>),         \
+            dim3((unsigned)((M / BMv) * nbn)), dim3(WMv * WNv * 64), 0,    \
+            stream, M, N, K, (const TY*)A, lda, (const TY*)B, ldb, (TY*)C, \
+            ldc, (int)(M / BMv), band, phase_mask)
     #define LAUNCH(TY, BETA, BK, BMv, WMv, WNv)                            \
         do {                                                               \
         g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(TY) == 4, BETA, BK, BMv,    \
                                         WMv * WNv, band, phase_mask};      \
-        hipLaunchKernelGGL((gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv>),\
-            dim3((unsigned)((M / BMv) * nbn)), dim3(WMv * WNv * 64), 0,    \
-            stream, M, N, K, (const TY*)A, lda, (const TY*)B, ldb, (TY*)C, \
-            ldc, (int)(M / BMv), band, phase_mask);                        \
+        const bool pipe = pitch32 && (loopsel >= 0 ? loopsel == 1          \
+                              : !(sizeof(TY) == 4 && BK == 16));           \
+        g_last_gemm_loop = pipe ? 1 : 0;                                   \
+        if (pipe) LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 1);             \
+        else      LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 0);             \
         } while (0)
     if (is_fp32) {
         if (beta_one) { if (bk32) LAUNCH(float, 1, 32, 128, 2, 4); else LAUNCH(float, 1, 16, 128, 2, 2); }
@@ -734,6 +973,7 @@ int mxk_gemm(int is_fp32, int beta_one,
         else          { if (bk32) LAUNCH(double, 0, 32, 128, 2, 4); else LAUNCH(double, 0, 16, 128, 2, 2); }
     }
     #undef LAUNCH
+    #undef LAUNCH_LOOP
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 

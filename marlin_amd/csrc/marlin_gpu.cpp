@@ -48,6 +48,7 @@ int mxk_transpose(int is_fp32, int64_t m, int64_t n, const void* in,
 int mxk_gemv(int is_fp32, int64_t m, int64_t n, int64_t lda, const void* A,
              const void* x, double* partial, void* y, hipStream_t stream);
 void mxk_last_gemm_config(mx_gemm_cfg_t* out);
+void mxk_last_gemm_loop(int* out);
 }
 
 #define HIP_OK(x)                                                        \
@@ -430,6 +431,12 @@ int mx_gemm_device_ex(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
 int mx_last_gemm_config(mx_ctx* c, mx_gemm_cfg_t* out) {
   if (!c || !out) return MX_EINVAL;
   mxk_last_gemm_config(out);
+  return MX_OK;
+}
+
+int mx_last_gemm_loop(mx_ctx* c, int* out) {
+  if (!c || !out) return MX_EINVAL;
+  mxk_last_gemm_loop(out);
   return MX_OK;
 }
 

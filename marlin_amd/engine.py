@@ -127,6 +127,7 @@ def _load():
                                            P(dbl)]),
         "mx_stats": (ctypes.c_int, [vp, P(MxStats)]),
         "mx_last_gemm_config": (ctypes.c_int, [vp, P(MxGemmCfg)]),
+        "mx_last_gemm_loop": (ctypes.c_int, [vp, P(ctypes.c_int)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -475,6 +476,14 @@ class Engine:
         _ck(lib().mx_last_gemm_config(self._ctx, ctypes.byref(cfg)),
             "mx_last_gemm_config")
         return {f: getattr(cfg, f) for f, _ in MxGemmCfg._fields_}
+
+    def last_gemm_loop(self):
+        """k-loop of the last plain GEMM launch: 1 = pipelined, 0 =
+        two-barrier (MARLIN_GEMM_LOOP=twobar)."""
+        out = ctypes.c_int(-1)
+        _ck(lib().mx_last_gemm_loop(self._ctx, ctypes.byref(out)),
+            "mx_last_gemm_loop")
+        return out.value
 
     # -- device-resident matrices (RDD.cache() analog) ----------------------
     def upload_matrix(self, a, fp32=False):
