@@ -77,6 +77,15 @@ int mx_dgemm(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
 int mx_sgemm(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
              const float* A, const float* B, float* C);
 
+/* C = op(A)·op(B), op(X) = X or X^T per trans_x in {0,1}, fp64
+ * (is_fp32 = 0) or fp32. Host buffers, tight col-major: A is m x k (k x m
+ * if trans_a), B is k x n (n x k if trans_b), C is m x n. Pad/H2D/GEMM/D2H
+ * inside, as mx_dgemm; a transposed operand is uploaded as stored and
+ * never copied into the other layout. m, k or n <= 0 is MX_EDIM. */
+int mx_gemm_op(mx_ctx* ctx, int is_fp32, int trans_a, int trans_b,
+               int64_t m, int64_t k, int64_t n,
+               const void* A, const void* B, void* C);
+
 /* fp32 multiply with fused epilogue (BASELINE config 5):
  * C_out = op(A*B) [+ add_c], op = transpose if transpose_c != 0.
  * If transpose_c: C is n x m col-major, add_c (optional, may be NULL)
@@ -190,6 +199,36 @@ int mx_gemm_device_ex(mx_ctx* ctx, int is_fp32, int beta_one, int64_t m,
                       int64_t k, int64_t n, const mx_dbuf* dA, int64_t lda,
                       const mx_dbuf* dB, int64_t ldb, mx_dbuf* dC,
                       int64_t ldc);
+
+/* Transposed-operand device GEMM: C (+)= op(A)·op(B); op(X) = X or X^T
+ * per trans_x in {0,1} (any other value is MX_EINVAL). A transposed
+ * operand is passed AS STORED, no transposed copy exists anywhere: the
+ * kernel stages it through LDS the way it stages the other operand.
+ * m, k, n are the dims of the product (op(A) m x k, op(B) k x n, C m x n).
+ *
+ * Pitch contract, extending the one above:
+ *   - trans_a: the A image is k x m col-major with lda >= k;
+ *   - trans_b: the B image is n x k col-major with ldb >= n;
+ *   - rows past the logical extent up to the pitch are never read;
+ *   - every pitch is still a multiple of 16 bytes, ldc >= m, and m, n
+ *     are multiples of 128, k of 16. Empty shapes and k == 0 behave as on
+ *     the plain entries.
+ * dA == dB (one buffer in both roles, e.g. the Gram matrix A^T·A) is
+ * allowed: both operands are read-only. dC must not alias either.
+ * (trans_a, trans_b) = (0,0) launches the very kernel instantiation
+ * mx_gemm_device_ex does. The transposed forms exist in the default
+ * kernel geometry only (bk 16, bm 128, 4 waves): MARLIN_GEMM_CFG=bk32 /
+ * =bm256 fall back to it for them, mx_last_gemm_config reports what ran;
+ * MARLIN_GEMM_LOOP, _BAND, _REMAP and _PHASE apply as usual. The result
+ * is bit-identical to the plain entry run on a materialised transpose.
+ * Stats (flops, gemm_ms, gemm_launches) as mx_gemm_device_ex. */
+int mx_gemm_device_op(mx_ctx* ctx, int is_fp32, int beta_one, int trans_a,
+                      int trans_b, int64_t m, int64_t k, int64_t n,
+                      const mx_dbuf* dA, int64_t lda, const mx_dbuf* dB,
+                      int64_t ldb, mx_dbuf* dC, int64_t ldc);
+/* op of the most recent plain GEMM launch (0,0 after an NN launch, and
+ * before the first launch) */
+int mx_last_gemm_op(mx_ctx* ctx, int* trans_a, int* trans_b);
 
 /* Introspection: the gemm_mfma_kernel instantiation and remap arguments
  * of the most recent plain GEMM launch in this process (any entry that

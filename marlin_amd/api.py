@@ -290,10 +290,11 @@ class DenseVecMatrix:
             raise ValueError(f"Argument with more than 65535 cols: {n}")
         eng = self._engine()
         dA = eng.upload_matrix(self._host())
-        dAT = eng.transpose_dd(dA)
-        G = eng.gemm_dd(dAT, dA)
+        # A^T·A on the one resident image: the kernel stages the
+        # transposed operand itself, so no transposed copy is held
+        G = eng.gemm_dd(dA, dA, trans_a=True)
         out = eng.download_matrix(G)
-        for d in (dA, dAT, G):
+        for d in (dA, G):
             d.free()
         return out
 

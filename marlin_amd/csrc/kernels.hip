@@ -66,6 +66,67 @@ DEVFN void glds16(const void* g, void* lds) {
 }
 
 // ---------------------------------------------------------------------------
+// The two LDS staging schemes, restated for the transposed operand forms
+// (default geometry only: BK = 16, 128-wide tile, 4 waves). An operand
+// tile is 128 (tile dimension d: row of op(A), column of op(B)) x 16 (k).
+//
+//   R  runs along d: source element (d, kk) at X[(kbase+kk)*ldx + d0 + d],
+//      LDS image [16][128], 16-byte chunk swizzle keyed on kk&1, fragment
+//      read img[kk*128 + swz(d)].        op(A) = A  and  op(B) = B^T.
+//   K  runs along k: source element (kk, d) at X[(d0+d)*ldx + kbase + kk],
+//      LDS image [128][16], chunk swizzle keyed on (d>>1)&7 (fp32: &3),
+//      fragment read img[d*16 + swz(kk)].  op(B) = B  and  op(A) = A^T.
+//
+// These are the A and B paths of gemm_mfma_kernel at BK 16 / BM 128 (whose
+// own code stays as it is for the untransposed forms), so a transposed
+// operand is staged exactly as the OTHER operand is today. The MFMA lane
+// map varies d by lane&15 and kk by lane>>4 for both operands, hence the
+// bank-conflict argument of each scheme (see the swizzle comment in the
+// kernel) holds unchanged whichever operand uses it: R reads are
+// conflict-free per 16-lane group with groups shifted by 32 banks, K reads
+// hit 32 distinct banks per ds_read_b64 group (fp32: 2-way worst case).
+// Per wave and tile both schemes move the same number of 16-byte DMA
+// pieces (fp64 4, fp32 2), so the vmcnt counts and the pipelined loop's
+// piece bookkeeping do not depend on the form.
+template <typename T> struct stage_r {
+    static constexpr int E = 16 / sizeof(T);
+    static constexpr int KPP = 64 * E / 128;     // k-columns per DMA piece
+    static constexpr int PIECES = 16 / KPP / 4;  // per wave and tile
+    DEVFN static int col(int wid, int i) { return (wid * PIECES + i) * KPP; }
+    DEVFN static int lane_k(int lane) { return lane / (128 / E); }
+    DEVFN static int lane_d(int lane, int kk) {  // swizzled d of the chunk
+        return ((lane % (128 / E)) ^ ((kk & 1) << (E == 2 ? 3 : 2))) * E;
+    }
+    DEVFN static int lds(int c) { return c * 128; }
+    DEVFN static int frag(int d, int kk) {
+        if constexpr (E == 2)
+            return kk * 128 + (((d >> 1) ^ ((kk & 1) << 3)) << 1) + (d & 1);
+        else
+            return kk * 128 + (((d >> 2) ^ ((kk & 1) << 2)) << 2) + (d & 3);
+    }
+};
+template <typename T> struct stage_k {
+    static constexpr int E = 16 / sizeof(T);
+    static constexpr int DPP = 64 * E / 16;      // d-columns per DMA piece
+    static constexpr int PIECES = 128 / DPP / 4; // per wave and tile
+    DEVFN static int col(int wid, int i) { return (wid * PIECES + i) * DPP; }
+    DEVFN static int lane_d(int lane) { return lane / (16 / E); }
+    DEVFN static int lane_k(int lane, int d) {   // swizzled kk of the chunk
+        if constexpr (E == 2)
+            return ((lane % 8) ^ ((d >> 1) & 7)) * E;
+        else
+            return ((lane % 4) ^ ((d >> 1) & 3)) * E;
+    }
+    DEVFN static int lds(int c) { return c * 16; }
+    DEVFN static int frag(int d, int kk) {
+        if constexpr (E == 2)
+            return d * 16 + (((kk >> 1) ^ ((d >> 1) & 7)) << 1) + (kk & 1);
+        else
+            return d * 16 + (((kk >> 2) ^ ((d >> 1) & 3)) << 2) + (kk & 3);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Main GEMM kernel. C[MxN] (+)= A[MxK] * B[KxN], col-major, padded pitches:
 // M a multiple of BM, N of 128, K of BK (the host pads to 128/16; the
 // launcher only selects BK=32 / BM=256 configs when the padded dims
@@ -92,7 +153,16 @@ DEVFN void glds16(const void* g, void* lds) {
 //      tile's DMA issue and the next tile's quad-0 fragment reads; DMA
 //      sources are wave-uniform running pointers plus loop-invariant
 //      32-bit lane offsets (see the comment above that loop).
-template <typename T, int BETA, int BK, int BM, int WM, int WN, int PIPE>
+//
+// TA / TB select op(A) = A^T / op(B) = B^T (default geometry only): A is
+// then stored k x m with lda the k-run pitch and staged by scheme K with
+// d = row; B is stored n x k and staged by scheme R with d = col (see
+// stage_r / stage_k above). The MFMA operand meaning stays
+// a = opA[row = l15][k = l4], b = opB[k = l4][col = l15], so every C
+// element sees the accumulation chain NN gives on a materialised
+// transpose. The TA = TB = 0 code is the untransposed kernel unchanged.
+template <typename T, int BETA, int BK, int BM, int WM, int WN, int PIPE,
+          int TA = 0, int TB = 0>
 __launch_bounds__(WM * WN * 64, 2)
 __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                                  const T* __restrict__ A, int64_t lda,
@@ -159,6 +229,12 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // XORed with (c >> BSH) & BMASK (fp32 uses its own masks; see below)
     constexpr int BMASK = BK / 2 - 1;
     constexpr int BSH = (BK == 16) ? 1 : 0;
+    using SR = stage_r<T>;
+    using SK = stage_k<T>;
+    static_assert(!(TA || TB) || (BK == 16 && BM == 128 && NWAVES == 4),
+                  "transposed forms exist in the default geometry only");
+    static_assert(!(TA || TB) || (SK::PIECES == A_GLDS && SR::PIECES == B_GLDS),
+                  "both schemes move the same pieces per wave and tile");
 
     // --- LDS bank-conflict swizzles (measured 8-way on the B-fragment
     // reads without them — profiles/r01 PMC: conflict cycles were 88% of
@@ -175,6 +251,16 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     //     B chunk ^ (c>>1)&3 -> 2-way worst case (was 8-way).
     auto issue_tile = [&](int kt, int buf) {
         const int64_t kbase = (int64_t)kt * BK;
+        if constexpr (TA) {
+            // A^T: A is k x m, runs along k -> scheme K with d = row
+            #pragma unroll
+            for (int i = 0; i < SK::PIECES; i++) {
+                int c = SK::col(wid, i);
+                int d = c + SK::lane_d(lane);
+                const T* g = A + (row0 + d) * lda + kbase + SK::lane_k(lane, d);
+                glds16(g, &As[buf * BK * BM + SK::lds(c)]);
+            }
+        } else
         if constexpr (BM * sizeof(T) >= 1024) {
             // >=1 glds per column: chunk q covers column q/CPC, piece q%CPC
             constexpr int CPC = BM * sizeof(T) / 1024;
@@ -207,6 +293,16 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                 glds16(g, &As[buf * BK * BM + c * BM]);
             }
         }
+        if constexpr (TB) {
+            // B^T: B is n x k, runs along n -> scheme R with d = col
+            #pragma unroll
+            for (int i = 0; i < SR::PIECES; i++) {
+                int c = SR::col(wid, i);
+                int kk = c + SR::lane_k(lane);
+                const T* g = B + (kbase + kk) * ldb + col0 + SR::lane_d(lane, kk);
+                glds16(g, &Bs[buf * BN * BK + SR::lds(c)]);
+            }
+        } else
         #pragma unroll
         for (int i = 0; i < B_GLDS; i++) {
             int c = (wid * B_GLDS + i) * B_COLS_PER_GLDS;
@@ -267,6 +363,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
             int rr = wm * (MT * 16) + mt * 16 + l15;
+            if constexpr (TA)
+                a[mt] = At[SK::frag(rr, kk)];
+            else
             if constexpr (E == 2)
                 a[mt] = At[kk * BM + (((rr >> 1) ^ ((kk & 1) << 3)) << 1)
                            + (rr & 1)];
@@ -277,6 +376,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
             int cb = wn * (NT * 16) + nt * 16 + l15;
+            if constexpr (TB)
+                b[nt] = Bt[SR::frag(cb, kk)];
+            else
             if constexpr (E == 2)
                 b[nt] = Bt[cb * BK
                            + ((((kk >> 1) ^ ((cb >> BSH) & BMASK)) << 1))
@@ -326,6 +428,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
             #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
                 int rr = wm * (MT * 16) + mt * 16 + l15;
+                if constexpr (TA)
+                    a[mt] = At[SK::frag(rr, kk)];
+                else
                 if constexpr (E == 2)
                     a[mt] = At[kk * BM + (((rr >> 1) ^ ((kk & 1) << 3)) << 1)
                                + (rr & 1)];
@@ -336,6 +441,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
             #pragma unroll
             for (int nt = 0; nt < NT; nt++) {
                 int cb = wn * (NT * 16) + nt * 16 + l15;
+                if constexpr (TB)
+                    b[nt] = Bt[SR::frag(cb, kk)];
+                else
                 if constexpr (E == 2)
                     b[nt] = Bt[cb * BK
                                + ((((kk >> 1) ^ ((cb >> BSH) & BMASK)) << 1))
@@ -398,6 +506,15 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     int a_lds[A_GLDS], b_lds[B_GLDS];            // LDS element offsets, buf 0
     #pragma unroll
     for (int i = 0; i < A_GLDS; i++) {
+        if constexpr (TA) {
+            // scheme K on A: what B's pieces are below, with lda for ldb
+            int c = SK::col(swid, i);
+            int d = c + SK::lane_d(lane);
+            a_lane[i] = ((uint32_t)SK::lane_d(lane) * (uint32_t)lda
+                         + (uint32_t)SK::lane_k(lane, d)) * (uint32_t)sizeof(T);
+            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
+            a_lds[i] = SK::lds(c);
+        } else
         if constexpr (BM * sizeof(T) >= 1024) {
             constexpr int CPC = BM * sizeof(T) / 1024;
             int q = swid * A_GLDS + i;
@@ -427,6 +544,15 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     }
     #pragma unroll
     for (int i = 0; i < B_GLDS; i++) {
+        if constexpr (TB) {
+            // scheme R on B: what A's pieces are above, with ldb for lda
+            int c = SR::col(swid, i);
+            int kk = c + SR::lane_k(lane);
+            b_lane[i] = ((uint32_t)SR::lane_k(lane) * (uint32_t)ldb
+                         + (uint32_t)SR::lane_d(lane, kk)) * (uint32_t)sizeof(T);
+            b_uni[i] = (int64_t)c * ldb * (int64_t)sizeof(T);
+            b_lds[i] = SR::lds(c);
+        } else {
         int c = (swid * B_GLDS + i) * B_COLS_PER_GLDS;
         int lane_col = lane / (BK / E);
         int lane_row;
@@ -440,12 +566,19 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                      + (uint32_t)lane_row) * (uint32_t)sizeof(T);
         b_uni[i] = (int64_t)c * ldb * (int64_t)sizeof(T);
         b_lds[i] = c * BK;
+        }
     }
 
-    const char* const pA0 = (const char*)(A + row0);           // tile 0
-    const char* const pB0 = (const char*)(B + col0 * ldb);
-    const int64_t stepA = (int64_t)BK * lda * (int64_t)sizeof(T);
-    constexpr int64_t stepB = (int64_t)BK * sizeof(T);
+    // tile 0 and the per-tile step of each running pointer: an operand
+    // whose runs follow k (B, A^T) starts at its tile's first column and
+    // steps BK elements; one whose runs follow d (A, B^T) starts at its
+    // tile's first row and steps BK columns of its pitch
+    const char* const pA0 = (const char*)(TA ? A + row0 * lda : A + row0);
+    const char* const pB0 = (const char*)(TB ? B + col0 : B + col0 * ldb);
+    const int64_t stepA = TA ? (int64_t)BK * (int64_t)sizeof(T)
+                             : (int64_t)BK * lda * (int64_t)sizeof(T);
+    const int64_t stepB = TB ? (int64_t)BK * ldb * (int64_t)sizeof(T)
+                             : (int64_t)BK * (int64_t)sizeof(T);
     const char* pA = pA0 + ph * stepA;       // tile the next issue loads
     const char* pB = pB0 + ph * stepB;
     int kt = ph;
@@ -892,15 +1025,27 @@ static inline bool pitch_ok(int64_t ld, int64_t rows, int64_t elems16) {
     return ld >= rows && ld % elems16 == 0;
 }
 
-int mxk_gemm(int is_fp32, int beta_one,
-             int64_t M, int64_t N, int64_t K,
-             const void* A, int64_t lda, const void* B, int64_t ldb,
-             void* C, int64_t ldc, hipStream_t stream) {
+// op(A), op(B) of that launch (mx_last_gemm_op): 1 = transposed
+static int g_last_gemm_op[2] = {0, 0};
+
+void mxk_last_gemm_op(int* trans_a, int* trans_b) {
+    *trans_a = g_last_gemm_op[0];
+    *trans_b = g_last_gemm_op[1];
+}
+
+// C (+)= op(A) * op(B). A transposed operand is the stored image of the
+// other shape: A^T is k x m (lda covers K), B^T is n x k (ldb covers N).
+int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
+                int64_t M, int64_t N, int64_t K,
+                const void* A, int64_t lda, const void* B, int64_t ldb,
+                void* C, int64_t ldc, hipStream_t stream) {
+    if ((trans_a | trans_b) & ~1) return -4;   // each is 0 or 1
     if (M < 0 || N < 0 || K < 0) return -4;
     if (M == 0 || N == 0) return 0;            // empty tile: nothing to do
     {
         const int64_t e16 = is_fp32 ? 4 : 2;   // elements per 16 bytes
-        if (!pitch_ok(lda, M, e16) || !pitch_ok(ldb, K, e16) ||
+        if (!pitch_ok(lda, trans_a ? K : M, e16) ||
+            !pitch_ok(ldb, trans_b ? N : K, e16) ||
             !pitch_ok(ldc, M, e16))
             return -4;
     }
@@ -929,6 +1074,8 @@ int mxk_gemm(int is_fp32, int beta_one,
     static const char* cfg = getenv("MARLIN_GEMM_CFG");
     bool bk32 = (K % 32 == 0) && cfg && cfg[0] == 'b' && cfg[1] == 'k';
     bool bm256 = (M % 256 == 0) && !is_fp32 && cfg && cfg[0] == 'b' && cfg[1] == 'm';
+    // the transposed forms exist in the default geometry only
+    if (trans_a || trans_b) bk32 = bm256 = false;
     // k-phase stagger mask (experiment; see kernel comment). 0 = off.
     static const char* phenv = getenv("MARLIN_GEMM_PHASE");
     int phase_mask = phenv ? atoi(phenv) : 0;
@@ -941,27 +1088,50 @@ int mxk_gemm(int is_fp32, int beta_one,
     // one loop everywhere (paired comparisons, tests). A pitch so large
     // that the pipelined loop's 32-bit per-lane DMA offsets (up to 15
     // columns of B, 1 of A, plus one 1 KiB run) could overflow always
-    // takes the two-barrier loop.
+    // takes the two-barrier loop. A transposed operand takes the other
+    // operand's offsets with its own pitch, so the one bound on both
+    // pitches covers every form.
     static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
     const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
                       : loopenv[0] == 'p' ? 1 : -1;
     const bool pitch32 = lda < ((int64_t)1 << 26) && ldb < ((int64_t)1 << 26);
-    #define LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, PIPE)                 \
+    #define LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, PIPE, TA, TB)         \
         hipLaunchKernelGGL(                                                \
-            (gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv, PIPE>),         \
+            (gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv, PIPE, TA, TB>), \
             dim3((unsigned)((M / BMv) * nbn)), dim3(WMv * WNv * 64), 0,    \
             stream, M, N, K, (const TY*)A, lda, (const TY*)B, ldb, (TY*)C, \
             ldc, (int)(M / BMv), band, phase_mask)
-    #define LAUNCH(TY, BETA, BK, BMv, WMv, WNv)                            \
+    #define LAUNCH_OP(TY, BETA, BK, BMv, WMv, WNv, TA, TB)                 \
         do {                                                               \
         g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(TY) == 4, BETA, BK, BMv,    \
                                         WMv * WNv, band, phase_mask};      \
         const bool pipe = pitch32 && (loopsel >= 0 ? loopsel == 1          \
                               : !(sizeof(TY) == 4 && BK == 16));           \
         g_last_gemm_loop = pipe ? 1 : 0;                                   \
-        if (pipe) LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 1);             \
-        else      LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 0);             \
+        g_last_gemm_op[0] = TA;                                            \
+        g_last_gemm_op[1] = TB;                                            \
+        if (pipe) LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 1, TA, TB);     \
+        else      LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 0, TA, TB);     \
         } while (0)
+    #define LAUNCH(TY, BETA, BK, BMv, WMv, WNv)                            \
+        LAUNCH_OP(TY, BETA, BK, BMv, WMv, WNv, 0, 0)
+    // transposed forms: default geometry, per type and beta
+    #define LAUNCH_T(TY, TA, TB)                                           \
+        do {                                                               \
+        if (beta_one) LAUNCH_OP(TY, 1, 16, 128, 2, 2, TA, TB);             \
+        else          LAUNCH_OP(TY, 0, 16, 128, 2, 2, TA, TB);             \
+        } while (0)
+    if (trans_a || trans_b) {
+        if (is_fp32) {
+            if (trans_a && trans_b) LAUNCH_T(float, 1, 1);
+            else if (trans_a)       LAUNCH_T(float, 1, 0);
+            else                    LAUNCH_T(float, 0, 1);
+        } else {
+            if (trans_a && trans_b) LAUNCH_T(double, 1, 1);
+            else if (trans_a)       LAUNCH_T(double, 1, 0);
+            else                    LAUNCH_T(double, 0, 1);
+        }
+    } else
     if (is_fp32) {
         if (beta_one) { if (bk32) LAUNCH(float, 1, 32, 128, 2, 4); else LAUNCH(float, 1, 16, 128, 2, 2); }
         else          { if (bk32) LAUNCH(float, 0, 32, 128, 2, 4); else LAUNCH(float, 0, 16, 128, 2, 2); }
@@ -972,9 +1142,19 @@ int mxk_gemm(int is_fp32, int beta_one,
         if (beta_one) { if (bk32) LAUNCH(double, 1, 32, 128, 2, 4); else LAUNCH(double, 1, 16, 128, 2, 2); }
         else          { if (bk32) LAUNCH(double, 0, 32, 128, 2, 4); else LAUNCH(double, 0, 16, 128, 2, 2); }
     }
+    #undef LAUNCH_T
+    #undef LAUNCH_OP
     #undef LAUNCH
     #undef LAUNCH_LOOP
     return (int)hipGetLastError() == 0 ? 0 : -2;
+}
+
+int mxk_gemm(int is_fp32, int beta_one,
+             int64_t M, int64_t N, int64_t K,
+             const void* A, int64_t lda, const void* B, int64_t ldb,
+             void* C, int64_t ldc, hipStream_t stream) {
+    return mxk_gemm_op(is_fp32, beta_one, 0, 0, M, N, K, A, lda, B, ldb, C,
+                       ldc, stream);
 }
 
 int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K,

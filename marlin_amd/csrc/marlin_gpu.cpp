@@ -25,12 +25,18 @@
 #include <utility>
 
 #include "../../include/marlin_gpu.h"
+#include "gemm_op_layout.h"
 
 // kernels.hip launchers
 extern "C" {
 int mxk_gemm(int is_fp32, int beta_one, int64_t M, int64_t N, int64_t K,
              const void* A, int64_t lda, const void* B, int64_t ldb,
              void* C, int64_t ldc, hipStream_t stream);
+int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
+                int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
+                const void* B, int64_t ldb, void* C, int64_t ldc,
+                hipStream_t stream);
+void mxk_last_gemm_op(int* trans_a, int* trans_b);
 int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K, const float* A,
                           int64_t lda, const float* B, int64_t ldb, float* C,
                           int64_t ldc, const float* addC, hipStream_t stream);
@@ -340,12 +346,13 @@ int mx_download2d_off(mx_ctx* c, void* dst, const mx_dbuf* src,
 // device-resident GEMM (padded pitches required)
 static int gemm_device(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                        int64_t k, int64_t n, const void* dA, int64_t lda,
-                       const void* dB, int64_t ldb, void* dC, int64_t ldc) {
+                       const void* dB, int64_t ldb, void* dC, int64_t ldc,
+                       int trans_a = 0, int trans_b = 0) {
   if (m % 128 || n % 128 || k % 16) return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  int rc = mxk_gemm(is_fp32, beta_one, m, n, k, dA, lda, dB, ldb, dC, ldc,
-                    c->s_gemm);
+  int rc = mxk_gemm_op(is_fp32, beta_one, trans_a, trans_b, m, n, k, dA, lda,
+                       dB, ldb, dC, ldc, c->s_gemm);
   if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
   HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
   HIP_OK(hipEventSynchronize(c->ev[1]));
@@ -428,6 +435,24 @@ int mx_gemm_device_ex(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                      ldb, dC->ptr, ldc);
 }
 
+// C (+)= op(A)·op(B) on device-resident images
+int mx_gemm_device_op(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
+                      int trans_b, int64_t m, int64_t k, int64_t n,
+                      const mx_dbuf* dA, int64_t lda, const mx_dbuf* dB,
+                      int64_t ldb, mx_dbuf* dC, int64_t ldc) {
+  if (!c || !dA || !dB || !dC) return MX_EINVAL;
+  c->st = {};
+  c->st.flops = 2.0 * m * k * n;
+  return gemm_device(c, is_fp32, beta_one, m, k, n, dA->ptr, lda, dB->ptr,
+                     ldb, dC->ptr, ldc, trans_a, trans_b);
+}
+
+int mx_last_gemm_op(mx_ctx* c, int* trans_a, int* trans_b) {
+  if (!c || !trans_a || !trans_b) return MX_EINVAL;
+  mxk_last_gemm_op(trans_a, trans_b);
+  return MX_OK;
+}
+
 int mx_last_gemm_config(mx_ctx* c, mx_gemm_cfg_t* out) {
   if (!c || !out) return MX_EINVAL;
   mxk_last_gemm_config(out);
@@ -443,14 +468,21 @@ int mx_last_gemm_loop(mx_ctx* c, int* out) {
 // ---------------------------------------------------------------------------
 // host-buffer whole-multiply entries: pad -> H2D -> kernel -> D2H.
 // elem = 8 (fp64) or 4 (fp32).
+// A is tight col-major m x k (k x m if trans_a), B k x n (n x k if
+// trans_b): each is uploaded as stored into its zero-padded image
+// (mx_gemm_op_layout), no transposed copy is made anywhere.
 static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                      int64_t k, int64_t n, const void* A, const void* B,
-                     void* C, int transpose_c, const void* addC) {
+                     void* C, int transpose_c, const void* addC,
+                     int trans_a = 0, int trans_b = 0) {
   if (!c || !A || !B || !C) return MX_EINVAL;
+  if ((trans_a | trans_b) & ~1) return MX_EINVAL;
   if (m <= 0 || k <= 0 || n <= 0) return MX_EDIM;
   const int64_t elem = is_fp32 ? 4 : 8;
   const int64_t mp = round_up(m, 128), np = round_up(n, 128),
                 kp = round_up(k, 16);
+  mx_op_image ia, ib, ic;
+  mx_gemm_op_layout(trans_a, trans_b, m, k, n, &ia, &ib, &ic);
   c->st = {};
   c->st.flops = 2.0 * m * k * n;
   c->st.bytes_moved = (double)elem * (m * k + k * n + m * n);
@@ -462,12 +494,14 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
   if ((rc = ensure(c, &c->wsC, mp * np * elem))) return rc;
 
   HIP_OK(hipEventRecord(c->ev[2], c->s_copy));
-  if (m != mp || k != kp) HIP_OK(hipMemsetAsync(c->wsA.ptr, 0, mp * kp * elem, c->s_copy));
-  if (k != kp || n != np) HIP_OK(hipMemsetAsync(c->wsB.ptr, 0, kp * np * elem, c->s_copy));
-  HIP_OK(hipMemcpy2DAsync(c->wsA.ptr, mp * elem, A, m * elem, m * elem, k,
-                          hipMemcpyHostToDevice, c->s_copy));
-  HIP_OK(hipMemcpy2DAsync(c->wsB.ptr, kp * elem, B, k * elem, k * elem, n,
-                          hipMemcpyHostToDevice, c->s_copy));
+  if (ia.padded()) HIP_OK(hipMemsetAsync(c->wsA.ptr, 0, ia.elems() * elem, c->s_copy));
+  if (ib.padded()) HIP_OK(hipMemsetAsync(c->wsB.ptr, 0, ib.elems() * elem, c->s_copy));
+  HIP_OK(hipMemcpy2DAsync(c->wsA.ptr, ia.pitch * elem, A, ia.rows * elem,
+                          ia.rows * elem, ia.cols, hipMemcpyHostToDevice,
+                          c->s_copy));
+  HIP_OK(hipMemcpy2DAsync(c->wsB.ptr, ib.pitch * elem, B, ib.rows * elem,
+                          ib.rows * elem, ib.cols, hipMemcpyHostToDevice,
+                          c->s_copy));
   if (beta_one) {
     if (m != mp || n != np) HIP_OK(hipMemsetAsync(c->wsC.ptr, 0, mp * np * elem, c->s_copy));
     HIP_OK(hipMemcpy2DAsync(c->wsC.ptr, mp * elem, C, m * elem, m * elem, n,
@@ -479,7 +513,7 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
   if (transpose_c) {
     // fused transpose(+add) epilogue path (fp32 only): addC is N x M on
     // host; stage it padded on device (reuse wsC tail? keep simple: own buf)
-    if (!is_fp32) return MX_EINVAL;
+    if (!is_fp32 || trans_a || trans_b) return MX_EINVAL;
     const float* dAdd = nullptr;
     if (addC) {
       if ((rc = ensure(c, &c->wsPA[0], np * mp * elem))) return rc;
@@ -505,8 +539,9 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                             hipMemcpyDeviceToHost, c->s_gemm));
     HIP_OK(hipStreamSynchronize(c->s_gemm));
   } else {
-    if ((rc = gemm_device(c, is_fp32, beta_one, mp, kp, np, c->wsA.ptr, mp,
-                          c->wsB.ptr, kp, c->wsC.ptr, mp)))
+    if ((rc = gemm_device(c, is_fp32, beta_one, mp, kp, np, c->wsA.ptr,
+                          ia.pitch, c->wsB.ptr, ib.pitch, c->wsC.ptr,
+                          ic.pitch, trans_a, trans_b)))
       return rc;
     HIP_OK(hipEventRecord(c->ev[4], c->s_gemm));
     HIP_OK(hipStreamWaitEvent(c->s_copy, c->ev[4], 0));
@@ -528,6 +563,11 @@ int mx_dgemm(mx_ctx* c, int64_t m, int64_t k, int64_t n, const double* A,
 int mx_sgemm(mx_ctx* c, int64_t m, int64_t k, int64_t n, const float* A,
              const float* B, float* C) {
   return gemm_host(c, 1, 0, m, k, n, A, B, C, 0, nullptr);
+}
+int mx_gemm_op(mx_ctx* c, int is_fp32, int trans_a, int trans_b, int64_t m,
+               int64_t k, int64_t n, const void* A, const void* B, void* C) {
+  return gemm_host(c, is_fp32 ? 1 : 0, 0, m, k, n, A, B, C, 0, nullptr,
+                   trans_a, trans_b);
 }
 int mx_sgemm_epilogue(mx_ctx* c, int64_t m, int64_t k, int64_t n,
                       const float* A, const float* B, float* C,

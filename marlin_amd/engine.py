@@ -128,6 +128,15 @@ def _load():
         "mx_stats": (ctypes.c_int, [vp, P(MxStats)]),
         "mx_last_gemm_config": (ctypes.c_int, [vp, P(MxGemmCfg)]),
         "mx_last_gemm_loop": (ctypes.c_int, [vp, P(ctypes.c_int)]),
+        "mx_gemm_device_op": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int,
+                                             i64, i64, i64, vp, i64, vp, i64,
+                                             vp, i64]),
+        "mx_gemm_op": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, i64, i64, i64, vp, vp,
+                                      vp]),
+        "mx_last_gemm_op": (ctypes.c_int, [vp, P(ctypes.c_int),
+                                           P(ctypes.c_int)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -193,6 +202,23 @@ def summa_kresident(m, k, n, nranks):
     unsplit for this job size -> the k-resident distributed layout
     applies (zero steady-state xGMI traffic; BASELINE config 4)."""
     return bool(lib().mx_summa_kresident(m, k, n, nranks))
+
+
+_MISMATCH = "Dimension mismatch during matrix-matrix multiplication"
+
+
+def gemm_op_shape(a_shape, b_shape, trans_a=False, trans_b=False):
+    """(m, k, n) of C = op(A)·op(B) for operands STORED with shapes
+    a_shape, b_shape (op(X) = X^T where trans_x): op(A) is m x k, op(B)
+    is k x n. Raises the multiply's dimension-mismatch ValueError when
+    the inner dimensions differ. Pure (no GPU)."""
+    am, an = a_shape
+    bm, bn = b_shape
+    m, k = (an, am) if trans_a else (am, an)
+    k2, n = (bn, bm) if trans_b else (bm, bn)
+    if k != k2:
+        raise ValueError(f"{_MISMATCH}: {k} vs {k2}")
+    return m, k, n
 
 
 def _fbuf(a, dtype):
@@ -263,7 +289,24 @@ class Engine:
         return tuple(v.value for v in vals)  # pr, pc, prow, pcol
 
     # -- whole multiplies ----------------------------------------------------
-    def dgemm(self, A, B):
+    def _gemm_op(self, A, B, dt, trans_a, trans_b):
+        """C = op(A)·op(B) through mx_gemm_op: A, B are passed as stored
+        (A is k x m where trans_a, B is n x k where trans_b)."""
+        A = np.asfortranarray(A, dtype=dt)
+        B = np.asfortranarray(B, dtype=dt)
+        m, k, n = gemm_op_shape(A.shape, B.shape, trans_a, trans_b)
+        C = np.empty((m, n), dtype=dt, order="F")
+        _ck(lib().mx_gemm_op(self._ctx, 1 if dt == np.float32 else 0,
+                             1 if trans_a else 0, 1 if trans_b else 0,
+                             m, k, n, A.ctypes.data_as(ctypes.c_void_p),
+                             B.ctypes.data_as(ctypes.c_void_p),
+                             C.ctypes.data_as(ctypes.c_void_p)),
+            "mx_gemm_op")
+        return C
+
+    def dgemm(self, A, B, trans_a=False, trans_b=False):
+        if trans_a or trans_b:
+            return self._gemm_op(A, B, np.float64, trans_a, trans_b)
         A = np.asfortranarray(A, dtype=np.float64)
         B = np.asfortranarray(B, dtype=np.float64)
         m, k = A.shape
@@ -283,7 +326,9 @@ class Engine:
                  f"{st['flops'] / max(st['gemm_ms'], 1e-9) / 1e9:.1f} TF/s)")
         return C
 
-    def sgemm(self, A, B):
+    def sgemm(self, A, B, trans_a=False, trans_b=False):
+        if trans_a or trans_b:
+            return self._gemm_op(A, B, np.float32, trans_a, trans_b)
         A = np.asfortranarray(A, dtype=np.float32)
         B = np.asfortranarray(B, dtype=np.float32)
         m, k = A.shape
@@ -477,6 +522,13 @@ class Engine:
             "mx_last_gemm_config")
         return {f: getattr(cfg, f) for f, _ in MxGemmCfg._fields_}
 
+    def last_gemm_op(self):
+        """(trans_a, trans_b) of the last plain GEMM launch."""
+        ta, tb = ctypes.c_int(-1), ctypes.c_int(-1)
+        _ck(lib().mx_last_gemm_op(self._ctx, ctypes.byref(ta),
+                                  ctypes.byref(tb)), "mx_last_gemm_op")
+        return ta.value, tb.value
+
     def last_gemm_loop(self):
         """k-loop of the last plain GEMM launch: 1 = pipelined, 0 =
         two-barrier (MARLIN_GEMM_LOOP=twobar)."""
@@ -554,29 +606,35 @@ class Engine:
             "mx_transpose_device")
         return DeviceMatrix(self, out, dm.n, dm.m, ncap, dm.fp32)
 
-    def gemm_dd(self, A, B, C=None, accumulate=False):
-        """Device-resident C (+)= A @ B on cached matrices. Pads are
-        zero, so padded-dim GEMM is exact; result C is a DeviceMatrix
-        with logical (A.m, B.n)."""
+    def gemm_dd(self, A, B, C=None, accumulate=False, trans_a=False,
+                trans_b=False):
+        """Device-resident C (+)= op(A) @ op(B) on cached matrices, op(X)
+        = X^T where trans_x: a transposed operand is used as stored, no
+        transposed copy is made. A DeviceMatrix image has its pitch and
+        its column capacity padded to 128 with zero pads, so every form
+        runs on the padded dims and stays exact; C is a DeviceMatrix with
+        the logical shape of the product, pitch roundup(m, 128), and
+        zero pads (it can feed the next GEMM in any role)."""
         assert A.fp32 == B.fp32
-        if A.n != B.m:
-            raise ValueError(
-                f"Dimension mismatch during matrix-matrix multiplication: "
-                f"{A.n} vs {B.m}")
-        kp = (A.n + 15) // 16 * 16
-        np_ = (B.n + 127) // 128 * 128
+        m, k, n = gemm_op_shape((A.m, A.n), (B.m, B.n), trans_a, trans_b)
+        mp = (m + 127) // 128 * 128      # A.pitch, or A's column capacity
+        kp = (k + 15) // 16 * 16
+        np_ = (n + 127) // 128 * 128     # B's column capacity, or B.pitch
         if C is None:
             assert not accumulate
-            cbuf = self.alloc(A.pitch * np_ * A.elem)
-            C = DeviceMatrix(self, cbuf, A.m, B.n, A.pitch, A.fp32)
-        assert C.pitch == A.pitch and C.m == A.m and C.n == B.n
-        # B must expose kp padded rows: its pitch is >= kp iff B.m pads ok
-        assert B.pitch >= kp
-        _ck(lib().mx_gemm_device_ex(self._ctx, 1 if A.fp32 else 0,
+            cbuf = self.alloc(mp * np_ * A.elem)
+            C = DeviceMatrix(self, cbuf, m, n, mp, A.fp32)
+        assert C.pitch == mp and C.m == m and C.n == n
+        # each image exposes its padded extent: the pitch covers the
+        # stored rows rounded to 128 (>= kp where k runs along the rows)
+        assert A.pitch >= (kp if trans_a else mp)
+        assert B.pitch >= (np_ if trans_b else kp)
+        _ck(lib().mx_gemm_device_op(self._ctx, 1 if A.fp32 else 0,
                                     1 if accumulate else 0,
-                                    A.pitch, kp, np_, A.buf, A.pitch,
+                                    1 if trans_a else 0, 1 if trans_b else 0,
+                                    mp, kp, np_, A.buf, A.pitch,
                                     B.buf, B.pitch, C.buf, C.pitch),
-            "mx_gemm_device_ex")
+            "mx_gemm_device_op")
         return C
 
     # -- device-resident bench path ------------------------------------------

@@ -231,21 +231,19 @@ def cholesky_decompose(dvm, mode="auto", base_size=1000):
         linvT = np.linalg.inv(L11).T                 # L11^-T (host, base)
         d_pos = eng.upload_matrix(linvT)
         d_neg = eng.upload_matrix(-linvT)
-        negT = {}
+        neg = {}
         for r in range(i + 1, nb):
             old = blk[(r, i)]
             l21 = eng.gemm_dd(old, d_pos)            # L21 panel
-            negp = eng.gemm_dd(old, d_neg)           # -L21
-            negT[r] = eng.transpose_dd(negp)         # -L21^T
-            negp.free()
+            neg[r] = eng.gemm_dd(old, d_neg)         # -L21
             old.free()
             blk[(r, i)] = l21
         for c in range(i + 1, nb):
             for r in range(c, nb):
-                # A22 += L21[r] @ (-L21[c]^T)
-                eng.gemm_dd(blk[(r, i)], negT[c], blk[(r, c)],
-                            accumulate=True)
-        for d in negT.values():
+                # A22 += L21[r] @ (-L21[c])^T, -L21[c] read as stored
+                eng.gemm_dd(blk[(r, i)], neg[c], blk[(r, c)],
+                            accumulate=True, trans_b=True)
+        for d in neg.values():
             d.free()
         d_pos.free()
         d_neg.free()

@@ -3,7 +3,9 @@
 // examples/BLAS3.scala:29-57). Args mirror MatrixMultiply.main:
 //
 //   marlinx bench  <m> <k> <n> [steps=3] [warmup=1]   random fp64 multiply
-//   marlinx verify <m> <k> <n>                        engine vs CPU check
+//   marlinx verify <m> <k> <n> [nn|tn|nt|tt]          engine vs CPU check
+//     (C = op(A)*op(B) through mx_gemm_op; t = that operand is stored
+//      transposed, k x m resp. n x k; default nn)
 //   marlinx epilogue <m> <k> <n>                      fp32 (A*B)^T + D check
 //     (config 5's fused transpose/add — BlockMatrix.scala:514-523 +
 //      :344-452 composed — through mx_sgemm_epilogue)
@@ -90,9 +92,15 @@ int main(int argc, char** argv) {
   }
 
   if (!strcmp(mode, "verify")) {
-    rc = mx_dgemm(ctx, m, k, n, A.data(), B.data(), C.data());
+    const char* form = argc > 5 ? argv[5] : "nn";
+    if (strlen(form) != 2 || !strchr("nt", form[0]) || !strchr("nt", form[1])) {
+      fprintf(stderr, "verify: form must be nn, tn, nt or tt\n");
+      return 2;
+    }
+    const int ta = form[0] == 't', tb = form[1] == 't';
+    rc = mx_gemm_op(ctx, 0, ta, tb, m, k, n, A.data(), B.data(), C.data());
     if (rc != MX_OK) {
-      fprintf(stderr, "mx_dgemm: %s\n", mx_strerror(rc));
+      fprintf(stderr, "mx_gemm_op: %s\n", mx_strerror(rc));
       return 1;
     }
     double maxrel = 0;
@@ -100,12 +108,15 @@ int main(int argc, char** argv) {
       for (int64_t i = 0; i < m; i++) {
         double acc = 0;
         for (int64_t l = 0; l < k; l++)
-          acc += A[l * m + i] * B[j * k + l];
+          acc += (ta ? A[i * k + l] : A[l * m + i]) *
+                 (tb ? B[l * n + j] : B[j * k + l]);
         double d = C[j * m + i] - acc;
         double rel = (d < 0 ? -d : d) / (acc < 0 ? -acc : acc);
         if (rel > maxrel) maxrel = rel;
       }
-    printf("verify %lldx%lldx%lld max_rel=%.3e %s\n", (long long)m,
+    // the plain form prints what it always has
+    printf("verify %s%s%lldx%lldx%lld max_rel=%.3e %s\n",
+           ta || tb ? form : "", ta || tb ? " " : "", (long long)m,
            (long long)k, (long long)n, maxrel,
            maxrel < 1e-10 ? "OK" : "FAIL");
     mx_shutdown(ctx);
