@@ -259,7 +259,13 @@ int mx_last_gemm_loop(mx_ctx* ctx, int* out);
 /* SUMMA on device-resident local shards (bench hot loop: inputs already
  * in HBM when the timed region starts). Shard pitches are the PADDED
  * sizes: A_local pitch roundup(my_m,128) x my_ka cols; B_local pitch
- * roundup(my_kb,16) x my_n cols; C_local pitch roundup(my_m,128). */
+ * roundup(my_kb,16) x my_n cols; C_local pitch roundup(my_m,128).
+ * C_local is written as the whole padded image roundup(my_m,128) x
+ * roundup(my_n,128). Pad contract: B_local's pad rows are never read and
+ * the panel pack zeroes the k pad and the columns my_n..roundup(my_n,128)
+ * of every B panel, so C_local's pad columns are exactly zero, and its
+ * pad rows are exactly zero whenever A_local's pad rows are zero (the
+ * image can feed the next device GEMM or transpose as it stands). */
 int mx_dgemm_summa_device(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
                           const mx_dbuf* dA_local, const mx_dbuf* dB_local,
                           mx_dbuf* dC_local);
@@ -270,6 +276,23 @@ int mx_sgemm_summa_device(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
 int mx_gemm_summa_kres_device(mx_ctx* ctx, int is_fp32, int64_t m, int64_t k,
                               int64_t n, const mx_dbuf* dA_local,
                               const mx_dbuf* dB_local, mx_dbuf* dC_local);
+/* Virtual rank: the panel loop of mx_*_summa_device for position
+ * (prow, pcol) of a pr x pc grid, on one GPU and without a communicator.
+ * dA_row holds the pc shards A_local of (prow, j), dB_col the pr shards
+ * B_local of (i, pcol), in the layouts above (an entry may be NULL where
+ * that shard is empty). Each panel is packed from its root's shard into
+ * this position's own panel buffers, which is what the broadcast would
+ * have delivered; everything else (plan, k-padding, double buffering,
+ * events, accumulate chain, pad contract) is the code the real entries
+ * run. kb_max is the panel width, 0 = default / MARLIN_SUMMA_KB.
+ * MX_EINVAL for a bad grid or position or NULL arrays; an empty shard
+ * (my_m == 0 or my_n == 0) returns MX_OK and launches nothing. mx_stats
+ * reports gemm_launches, comm_ms == 0. */
+int mx_gemm_summa_virtual(mx_ctx* ctx, int is_fp32, int pr, int pc, int prow,
+                          int pcol, int64_t m, int64_t k, int64_t n,
+                          const mx_dbuf* const* dA_row,
+                          const mx_dbuf* const* dB_col, mx_dbuf* dC_local,
+                          int64_t kb_max);
 
 /* Restore the zero-pad invariant of a rows_total x cols_total padded
  * image (pitch ld) whose logical content is m x n: pads outside m x n

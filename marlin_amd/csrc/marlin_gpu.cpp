@@ -661,16 +661,79 @@ struct ev_pool {
   }
 };
 
-static int summa_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
-                        int64_t n, const void* dA, const void* dB, void* dC) {
-  if (!c->have_comm) return MX_ENOCOMM;
+// panel width: overlap granularity of the comm/MFMA pipeline.
+// Default 2048 (measured: the 1-rank panel-loop machinery runs at
+// 98.9% of the monolithic GEMM rate at KB=2048 vs 97.2% at 4096 —
+// profiles/r02_experiments.md; broadcasts still hide under the
+// ~3 ms per-panel GEMM at 8 GPUs). MARLIN_SUMMA_KB overrides (latched
+// on first use).
+static int64_t default_summa_kb() {
+  static const char* kbenv = getenv("MARLIN_SUMMA_KB");
+  return kbenv && atoll(kbenv) > 0 ? atoll(kbenv) : 2048;
+}
+
+// One grid position of the panel loop. srcA[j] is A_local of (prow, j) and
+// srcB[i] is B_local of (i, pcol) where this process holds that shard, or
+// nullptr where it does not: a panel is packed here exactly when its root's
+// shard is present. A real rank holds only its own shard (srcA[pcol],
+// srcB[prow]) and receives the other panels through the broadcasts; the
+// virtual entry holds every shard of its grid row and column and issues no
+// broadcast, so the pack delivers what the broadcast would have.
+struct summa_pos {
+  int pr, pc, prow, pcol;
+  const void* const* srcA;  // pc entries
+  const void* const* srcB;  // pr entries
+  bool bcast;               // ncclBroadcast each panel (real, nranks > 1)
+};
+
+// Pack one k-panel into this position's panel buffers (comm stream):
+// k-padded to kbp, A pitch mip, B pitch kbp with all njp columns defined.
+static int pack_panel(mx_ctx* c, const summa_pos& g, const panel_t& pan,
+                      int64_t k, int64_t elem, int64_t mip, int64_t nj,
+                      int64_t njp, void* pa, void* pb) {
+  const int64_t kb = pan.k1 - pan.k0;
+  const int64_t kbp = round_up(kb, 16);
+  if (kbp != kb) {
+    if (mip > 0)
+      HIP_OK(hipMemsetAsync(pa, 0, (size_t)(mip * kbp * elem), c->s_comm));
+    if (njp > 0)
+      HIP_OK(hipMemsetAsync(pb, 0, (size_t)(kbp * njp * elem), c->s_comm));
+  }
+  const void* dA = g.srcA[pan.rootA];
+  if (dA && mip > 0) {
+    // A panel: k-cols [k0-ka_off, k1-ka_off) of the root's A_local (pitch
+    // mip) are contiguous -> one copy into the packed panel (pitch mip)
+    const int64_t ka_off = mx_slab_off(k, g.pc, pan.rootA);
+    const char* src = (const char*)dA + (pan.k0 - ka_off) * mip * elem;
+    HIP_OK(hipMemcpyAsync(pa, src, (size_t)(mip * kb * elem),
+                          hipMemcpyDeviceToDevice, c->s_comm));
+  }
+  const void* dB = g.srcB[pan.rootB];
+  if (dB && njp > 0) {
+    // B panel: k-rows [k0-kb_off, k1-kb_off) of the root's B_local (pitch
+    // kbi_p): strided 2D copy into packed pitch kbp
+    const int64_t kb_off = mx_slab_off(k, g.pr, pan.rootB);
+    const int64_t kbi_p = round_up(mx_slab_len(k, g.pr, pan.rootB), 16);
+    const char* src = (const char*)dB + (pan.k0 - kb_off) * elem;
+    if (nj > 0)
+      HIP_OK(hipMemcpy2DAsync(pb, kbp * elem, src, kbi_p * elem, kb * elem,
+                              nj, hipMemcpyDeviceToDevice, c->s_comm));
+    // the copy defines nj columns only: an aligned panel skipped the
+    // memset above, so columns nj..njp would keep whatever the workspace
+    // held and reach C_local's pad columns
+    if (kbp == kb && nj < njp)
+      HIP_OK(hipMemsetAsync((char*)pb + kbp * nj * elem, 0,
+                            (size_t)(kbp * (njp - nj) * elem), c->s_comm));
+  }
+  return MX_OK;
+}
+
+static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
+                      int64_t k, int64_t n, void* dC, int64_t kb_max) {
   const int64_t elem = is_fp32 ? 4 : 8;
   const ncclDataType_t nty = is_fp32 ? ncclFloat32 : ncclFloat64;
-  const int64_t mi = mx_slab_len(m, c->pr, c->prow);
-  const int64_t nj = mx_slab_len(n, c->pc, c->pcol);
-  const int64_t kbi = mx_slab_len(k, c->pr, c->prow);   // B k-rows here
-  const int64_t ka_off = mx_slab_off(k, c->pc, c->pcol);
-  const int64_t kb_off = mx_slab_off(k, c->pr, c->prow);
+  const int64_t mi = mx_slab_len(m, g.pr, g.prow);
+  const int64_t nj = mx_slab_len(n, g.pc, g.pcol);
   const int64_t mip = round_up(mi, 128), njp = round_up(nj, 128);
   // Empty local shard (e.g. m < pr on tiny inputs): the reference path
   // handles any size, so this rank must still take part in every panel
@@ -679,18 +742,12 @@ static int summa_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
   const bool has_tile = mip > 0 && njp > 0;
   // local shard pitches ARE the padded sizes (bench fills them that way;
   // host entry packs them that way)
-  // panel width: overlap granularity of the comm/MFMA pipeline.
-  // Default 2048 (measured: the 1-rank panel-loop machinery runs at
-  // 98.9% of the monolithic GEMM rate at KB=2048 vs 97.2% at 4096 —
-  // profiles/r02_experiments.md; broadcasts still hide under the
-  // ~3 ms per-panel GEMM at 8 GPUs). MARLIN_SUMMA_KB overrides.
-  static const char* kbenv = getenv("MARLIN_SUMMA_KB");
-  const int64_t kb_max = kbenv && atoll(kbenv) > 0 ? atoll(kbenv) : 2048;
-  auto panels = plan_panels(k, c->pr, c->pc, kb_max);
+  auto panels = plan_panels(k, g.pr, g.pc, kb_max);
 
   c->st = {};
   c->st.flops = 2.0 * m * k * n;  // whole-job flops (rank-aggregate metric)
   c->st.bytes_moved = (double)elem * (m * k + k * n + m * n);
+  if (!has_tile && !g.bcast) return MX_OK;  // nobody waits for this position
 
   HIP_OK(hipSetDevice(c->device));
   int rc;
@@ -715,36 +772,16 @@ static int summa_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
   for (size_t p = 0; p < panels.size(); p++) {
     const panel_t& pan = panels[p];
     const int buf = (int)(p & 1);
-    const int64_t kb = pan.k1 - pan.k0;
-    const int64_t kbp = round_up(kb, 16);
+    const int64_t kbp = round_up(pan.k1 - pan.k0, 16);
     void* pa = c->wsPA[buf].ptr;
     void* pb = c->wsPB[buf].ptr;
 
     // comm stream: wait until the GEMM that read this buffer 2 panels ago
     // is done, then pack (root) and broadcast.
     HIP_OK(hipStreamWaitEvent(c->s_comm, c->ev[8 + buf], 0));
-    if (kbp != kb) {
-      if (mip > 0)
-        HIP_OK(hipMemsetAsync(pa, 0, (size_t)(mip * kbp * elem), c->s_comm));
-      if (njp > 0)
-        HIP_OK(hipMemsetAsync(pb, 0, (size_t)(kbp * njp * elem), c->s_comm));
-    }
-    if (c->pcol == pan.rootA && mip > 0) {
-      // A panel: k-cols [k0-ka_off, k1-ka_off) of A_local (pitch mip) are
-      // contiguous -> strided copy into packed panel (pitch mip, kb cols)
-      const char* src = (const char*)dA + (pan.k0 - ka_off) * mip * elem;
-      HIP_OK(hipMemcpyAsync(pa, src, (size_t)(mip * kb * elem),
-                            hipMemcpyDeviceToDevice, c->s_comm));
-    }
-    if (c->prow == pan.rootB && njp > 0 && kbi > 0) {
-      // B panel: k-rows [k0-kb_off, k1-kb_off) of B_local (pitch kbi_p):
-      // strided 2D copy into packed pitch kbp
-      const int64_t kbi_p = round_up(kbi, 16);
-      const char* src = (const char*)dB + (pan.k0 - kb_off) * elem;
-      HIP_OK(hipMemcpy2DAsync(pb, kbp * elem, src, kbi_p * elem, kb * elem,
-                              nj, hipMemcpyDeviceToDevice, c->s_comm));
-    }
-    if (c->nranks > 1) {
+    if ((rc = pack_panel(c, g, pan, k, elem, mip, nj, njp, pa, pb)))
+      return rc;
+    if (g.bcast) {
       hipEvent_t c0 = tev.mk(), c1 = tev.mk();
       HIP_OK(hipEventRecord(c0, c->s_comm));
       RCCL_OK(ncclGroupStart());
@@ -786,6 +823,48 @@ static int summa_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
     c->st.comm_ms += ms;
   }
   return MX_OK;
+}
+
+// real entries: geometry from the context, only this rank's shards present
+static int summa_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
+                        int64_t n, const void* dA, const void* dB, void* dC) {
+  if (!c->have_comm) return MX_ENOCOMM;
+  std::vector<const void*> srcA(c->pc, nullptr), srcB(c->pr, nullptr);
+  srcA[c->pcol] = dA;
+  srcB[c->prow] = dB;
+  // a rank always joins the broadcasts, an empty one included; on one rank
+  // the loop still runs (and records its events) as it always has
+  const summa_pos g = {c->pr, c->pc, c->prow, c->pcol, srcA.data(),
+                       srcB.data(), c->nranks > 1};
+  return summa_loop(c, is_fp32, g, m, k, n, dC, default_summa_kb());
+}
+
+// Virtual rank: the same loop at an arbitrary position of a pr x pc grid on
+// one GPU, every panel packed from its root's shard instead of broadcast.
+int mx_gemm_summa_virtual(mx_ctx* c, int is_fp32, int pr, int pc, int prow,
+                          int pcol, int64_t m, int64_t k, int64_t n,
+                          const mx_dbuf* const* dA_row,
+                          const mx_dbuf* const* dB_col, mx_dbuf* dC_local,
+                          int64_t kb_max) {
+  if (!c || !dA_row || !dB_col || !dC_local) return MX_EINVAL;
+  if (pr <= 0 || pc <= 0 || prow < 0 || prow >= pr || pcol < 0 || pcol >= pc)
+    return MX_EINVAL;
+  if (m <= 0 || k <= 0 || n <= 0 || kb_max < 0) return MX_EINVAL;
+  // every non-empty shard of the grid row / column must be there
+  const bool empty = mx_slab_len(m, pr, prow) == 0 ||
+                     mx_slab_len(n, pc, pcol) == 0;
+  std::vector<const void*> srcA(pc, nullptr), srcB(pr, nullptr);
+  for (int j = 0; j < pc; j++) {
+    if (dA_row[j]) srcA[j] = dA_row[j]->ptr;
+    else if (!empty && mx_slab_len(k, pc, j) > 0) return MX_EINVAL;
+  }
+  for (int i = 0; i < pr; i++) {
+    if (dB_col[i]) srcB[i] = dB_col[i]->ptr;
+    else if (!empty && mx_slab_len(k, pr, i) > 0) return MX_EINVAL;
+  }
+  const summa_pos g = {pr, pc, prow, pcol, srcA.data(), srcB.data(), false};
+  return summa_loop(c, is_fp32, g, m, k, n, dC_local->ptr,
+                    kb_max > 0 ? kb_max : default_summa_kb());
 }
 
 // ---------------------------------------------------------------------------

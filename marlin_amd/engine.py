@@ -99,6 +99,8 @@ def _load():
                                                P(flt), P(flt)]),
         "mx_gemm_summa_kres_device": (ctypes.c_int, [vp, ctypes.c_int, i64,
                                                      i64, i64, vp, vp, vp]),
+        "mx_gemm_summa_virtual": (ctypes.c_int, [vp] + [ctypes.c_int] * 5
+                                  + [i64, i64, i64, P(vp), P(vp), vp, i64]),
         "mx_zero_pad": (ctypes.c_int, [vp, vp, i64, i64, i64, i64, i64,
                                        ctypes.c_int]),
         "mx_download_off": (ctypes.c_int, [vp, vp, vp, i64, i64]),
@@ -477,6 +479,20 @@ class Engine:
         _ck(lib().mx_gemm_summa_kres_device(self._ctx, 1 if fp32 else 0,
                                             m, k, n, dA, dB, dC),
             "mx_gemm_summa_kres_device")
+
+    def gemm_summa_virtual(self, pr, pc, prow, pcol, m, k, n, dA_row, dB_col,
+                           dC, kb_max=0, fp32=False):
+        """The SUMMA panel loop at position (prow, pcol) of a pr x pc grid
+        on this one GPU: dA_row are the pc A shards of grid row prow,
+        dB_col the pr B shards of grid column pcol (None where a shard is
+        empty); panels are packed from their root's shard instead of
+        being broadcast."""
+        assert len(dA_row) == pc and len(dB_col) == pr
+        arow = (ctypes.c_void_p * pc)(*dA_row)
+        bcol = (ctypes.c_void_p * pr)(*dB_col)
+        _ck(lib().mx_gemm_summa_virtual(self._ctx, 1 if fp32 else 0, pr, pc,
+                                        prow, pcol, m, k, n, arow, bcol, dC,
+                                        kb_max), "mx_gemm_summa_virtual")
 
     def zero_pad(self, dbuf, rows_total, cols_total, ld, m, n, fp32=False):
         _ck(lib().mx_zero_pad(self._ctx, dbuf, rows_total, cols_total, ld,

@@ -189,6 +189,48 @@ def test_gemm_argument_guards(eng):
         eng.free(d)
 
 
+@pytest.mark.parametrize("beta", [0, 1], ids=["b0", "b1"])
+@pytest.mark.parametrize("fp32", [0, 1], ids=["f64", "f32"])
+def test_gemm_k_zero_effect(eng, fp32, beta):
+    # k == 0 launches no kernel: C = 0 is a 2-D memset of the M x N
+    # interior through pitch ldc (pad rows and the trailing column keep
+    # their bits), C += 0 touches nothing. C is prefilled as in
+    # run_gemm_case.
+    _require_healthy()
+    import numpy as np
+    M, N = 256, 128
+    ldc = M + _exact.PAD
+    dt = _exact.dtype_of(fp32)
+    c = _exact.Case(fp32, beta, M, N, 16)
+    nan = _exact._nan(dt)
+    sentinel = dt(_exact.FINITE_SENTINEL) if beta else nan
+    cimg = (_exact._padded(_exact.gemm_inputs(c)[2], ldc, 1, sentinel) if beta
+            else _exact._filled(ldc, N + 1, nan))
+    bufs = []
+    try:
+        d = eng.alloc(64)               # A and B: never read at k == 0
+        bufs.append(d)
+        dC = _exact._dev(eng, cimg, bufs)
+        rc = E.lib().mx_gemm_device_ex(eng._ctx, fp32, beta, M, 0, N, d,
+                                       M + _exact.PAD, d, _exact.PAD, dC, ldc)
+        if rc == -2:
+            _GPU_POISONED.append("k == 0: HIP runtime failure in-process")
+        assert rc == 0
+        got = np.empty_like(cimg)
+        eng.download(got, dC, got.nbytes)
+    finally:
+        for b in bufs:
+            eng.free(b)
+    gbits, cbits = _exact._bits(got), _exact._bits(cimg)
+    if beta:
+        assert (gbits == cbits).all()
+    else:
+        assert (gbits[:M, :N] == 0).all()            # exactly +0.0
+        sbits = sentinel.view(_exact.UINT[dt])
+        assert (gbits[M:, :] == sbits).all()
+        assert (gbits[:, N:] == sbits).all()
+
+
 def test_epilogue_argument_guards(eng):
     _require_healthy()
     EINVAL = -4
