@@ -19,6 +19,11 @@
 //     DMA addresses are running wave-uniform pointers + constant lane
 //     offsets. The earlier two-barrier loop stays selectable
 //     (MARLIN_GEMM_LOOP=twobar) and is still fp32/BK=16's default.
+//   - The staging layout (DMA source per lane, LDS image, swizzles,
+//     fragment reads) is stated once, in gemm_stage.h, for every type,
+//     geometry and operand form; both loops go through it. The fused
+//     transpose/add epilogue of config 5 is the EPI parameter of the one
+//     GEMM template.
 //   - All matrices COLUMN-MAJOR with padded leading dims (multiples of the
 //     tile) — the host pads, so the kernel has no edge paths.
 //   - Grid is remapped into column bands so the ~512 resident blocks share
@@ -65,66 +70,47 @@ DEVFN void glds16(const void* g, void* lds) {
         (__attribute__((address_space(3))) uint32_t*)lds, 16, 0, 0);
 }
 
-// ---------------------------------------------------------------------------
-// The two LDS staging schemes, restated for the transposed operand forms
-// (default geometry only: BK = 16, 128-wide tile, 4 waves). An operand
-// tile is 128 (tile dimension d: row of op(A), column of op(B)) x 16 (k).
-//
-//   R  runs along d: source element (d, kk) at X[(kbase+kk)*ldx + d0 + d],
-//      LDS image [16][128], 16-byte chunk swizzle keyed on kk&1, fragment
-//      read img[kk*128 + swz(d)].        op(A) = A  and  op(B) = B^T.
-//   K  runs along k: source element (kk, d) at X[(d0+d)*ldx + kbase + kk],
-//      LDS image [128][16], chunk swizzle keyed on (d>>1)&7 (fp32: &3),
-//      fragment read img[d*16 + swz(kk)].  op(B) = B  and  op(A) = A^T.
-//
-// These are the A and B paths of gemm_mfma_kernel at BK 16 / BM 128 (whose
-// own code stays as it is for the untransposed forms), so a transposed
-// operand is staged exactly as the OTHER operand is today. The MFMA lane
-// map varies d by lane&15 and kk by lane>>4 for both operands, hence the
-// bank-conflict argument of each scheme (see the swizzle comment in the
-// kernel) holds unchanged whichever operand uses it: R reads are
-// conflict-free per 16-lane group with groups shifted by 32 banks, K reads
-// hit 32 distinct banks per ds_read_b64 group (fp32: 2-way worst case).
-// Per wave and tile both schemes move the same number of 16-byte DMA
-// pieces (fp64 4, fp32 2), so the vmcnt counts and the pipelined loop's
-// piece bookkeeping do not depend on the form.
-template <typename T> struct stage_r {
-    static constexpr int E = 16 / sizeof(T);
-    static constexpr int KPP = 64 * E / 128;     // k-columns per DMA piece
-    static constexpr int PIECES = 16 / KPP / 4;  // per wave and tile
-    DEVFN static int col(int wid, int i) { return (wid * PIECES + i) * KPP; }
-    DEVFN static int lane_k(int lane) { return lane / (128 / E); }
-    DEVFN static int lane_d(int lane, int kk) {  // swizzled d of the chunk
-        return ((lane % (128 / E)) ^ ((kk & 1) << (E == 2 ? 3 : 2))) * E;
+// The LDS staging layout (schemes R and K: DMA source per lane, LDS image,
+// swizzles, fragment reads) is stated once, in gemm_stage.h.
+#define STAGE_FN DEVFN
+#include "gemm_stage.h"
+
+// One wave's DMA of its pieces of one operand tile into the LDS image at
+// lds[img ...]; origin = the tile's first element (S::origin_elems).
+template <class S, typename T>
+DEVFN void issue_pieces(const char* origin, int64_t ld, T* lds, int img,
+                        int wid, int lane) {
+    #pragma unroll
+    for (int i = 0; i < S::PIECES; i++) {
+        const stage_piece p = S::piece(wid, i, lane);
+        glds16(origin + S::uni_bytes(p, ld) + S::lane_bytes(p, ld),
+               &lds[img + p.lds]);
     }
-    DEVFN static int lds(int c) { return c * 128; }
-    DEVFN static int frag(int d, int kk) {
-        if constexpr (E == 2)
-            return kk * 128 + (((d >> 1) ^ ((kk & 1) << 3)) << 1) + (d & 1);
-        else
-            return kk * 128 + (((d >> 2) ^ ((kk & 1) << 2)) << 2) + (d & 3);
+}
+
+// Block remap: column bands of |band| block-cols, split into 8x8 block
+// supertiles (band == 8 normally). Within a supertile the 8 blocks landing
+// on one XCD (dispatch places block b on XCD b%8, and all the stride terms
+// are multiples of 8) form one COLUMN: each XCD's L2 re-reads one B tile 8x
+// and a contiguous 8-row A panel. band < 0: plain bm-fastest bands (A/B
+// comparison fallback).
+DEVFN void block_remap(int id, int nbn, int nbm, int band, int& bm, int& bn) {
+    int abands = band < 0 ? -band : band;
+    int per_band = nbm * abands;
+    int b0 = id / per_band;
+    int w = id - b0 * per_band;
+    int first_bn = b0 * abands;
+    int bw = min(abands, nbn - first_bn);
+    if (band < 0) {                      // plain band order
+        bn = first_bn + w / nbm;
+        bm = w % nbm;
+    } else {                             // supertiled band order
+        int sh = 8 * bw;
+        int t = w / sh, l = w - t * sh;
+        bm = t * 8 + l / bw;
+        bn = first_bn + l % bw;
     }
-};
-template <typename T> struct stage_k {
-    static constexpr int E = 16 / sizeof(T);
-    static constexpr int DPP = 64 * E / 16;      // d-columns per DMA piece
-    static constexpr int PIECES = 128 / DPP / 4; // per wave and tile
-    DEVFN static int col(int wid, int i) { return (wid * PIECES + i) * DPP; }
-    DEVFN static int lane_d(int lane) { return lane / (16 / E); }
-    DEVFN static int lane_k(int lane, int d) {   // swizzled kk of the chunk
-        if constexpr (E == 2)
-            return ((lane % 8) ^ ((d >> 1) & 7)) * E;
-        else
-            return ((lane % 4) ^ ((d >> 1) & 3)) * E;
-    }
-    DEVFN static int lds(int c) { return c * 16; }
-    DEVFN static int frag(int d, int kk) {
-        if constexpr (E == 2)
-            return d * 16 + (((kk >> 1) ^ ((d >> 1) & 7)) << 1) + (kk & 1);
-        else
-            return d * 16 + (((kk >> 2) ^ ((d >> 1) & 3)) << 2) + (kk & 3);
-    }
-};
+}
 
 // ---------------------------------------------------------------------------
 // Main GEMM kernel. C[MxN] (+)= A[MxK] * B[KxN], col-major, padded pitches:
@@ -154,15 +140,23 @@ template <typename T> struct stage_k {
 //      sources are wave-uniform running pointers plus loop-invariant
 //      32-bit lane offsets (see the comment above that loop).
 //
-// TA / TB select op(A) = A^T / op(B) = B^T (default geometry only): A is
-// then stored k x m with lda the k-run pitch and staged by scheme K with
-// d = row; B is stored n x k and staged by scheme R with d = col (see
-// stage_r / stage_k above). The MFMA operand meaning stays
+// TA / TB select op(A) = A^T / op(B) = B^T: A is then stored k x m with
+// lda the k-run pitch and staged by scheme K with d = row; B is stored
+// n x k and staged by scheme R with d = col. A transposed operand is thus
+// staged exactly as the other operand is untransposed; both schemes move
+// the same number of pieces per wave and tile, so the vmcnt counts do not
+// depend on the form. The MFMA operand meaning stays
 // a = opA[row = l15][k = l4], b = opB[k = l4][col = l15], so every C
 // element sees the accumulation chain NN gives on a materialised
-// transpose. The TA = TB = 0 code is the untransposed kernel unchanged.
+// transpose. The launcher instantiates the transposed forms in the
+// default geometry only.
+//
+// EPI selects the epilogue: EPI_STORE writes C (m x n); EPI_TN_ADD writes
+// C_out[n x m] = (A*B)^T (+ addC) — see the end of the kernel.
+enum { EPI_STORE = 0, EPI_TN_ADD = 1 };
+
 template <typename T, int BETA, int BK, int BM, int WM, int WN, int PIPE,
-          int TA = 0, int TB = 0>
+          int TA = 0, int TB = 0, int EPI = EPI_STORE>
 __launch_bounds__(WM * WN * 64, 2)
 __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                                  const T* __restrict__ A, int64_t lda,
@@ -170,40 +164,22 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                                  T* __restrict__ C, int64_t ldc,
                                  int nbm /* grid rows = M/BM */,
                                  int band /* column-band width in blocks */,
-                                 int phase_mask /* k-phase stagger mask */) {
+                                 int phase_mask /* k-phase stagger mask */,
+                                 const T* __restrict__ addC /* EPI_TN_ADD */) {
     constexpr int BN = 128;
     constexpr int NWAVES = WM * WN;
-    constexpr int E = 16 / sizeof(T);       // elems per 16B glds chunk
     constexpr int MT = (BM / WM) / 16;      // 16x16 frags per wave, m
     constexpr int NT = (BN / WN) / 16;      // 16x16 frags per wave, n
     using ACC = typename acc_t<T>::type;
+    using SA = std::conditional_t<TA != 0, stage_k<T, BM, BK, NWAVES>,
+                                           stage_r<T, BM, BK, NWAVES>>;
+    using SB = std::conditional_t<TB != 0, stage_r<T, BN, BK, NWAVES>,
+                                           stage_k<T, BN, BK, NWAVES>>;
+    constexpr int P = SA::PIECES + SB::PIECES;   // DMA pieces per wave, tile
 
-    // --- block remap: column bands of `band` block-cols, split into 8x8
-    // block supertiles (band == 8 normally). Within a supertile the 8
-    // blocks landing on one XCD (dispatch places block b on XCD b%8, and
-    // all the stride terms are multiples of 8) form one COLUMN: each
-    // XCD's L2 re-reads one B tile 8x and a contiguous 8-row A panel.
-    // band < 0: plain bm-fastest bands (A/B comparison fallback).
-    int id = blockIdx.x;
+    const int id = blockIdx.x;
     int bn, bm;
-    {
-        int abands = band < 0 ? -band : band;
-        int nbn = (int)(N / BN);
-        int per_band = nbm * abands;
-        int b0 = id / per_band;
-        int w = id - b0 * per_band;
-        int first_bn = b0 * abands;
-        int bw = min(abands, nbn - first_bn);
-        if (band < 0) {                      // plain band order
-            bn = first_bn + w / nbm;
-            bm = w % nbm;
-        } else {                             // supertiled band order
-            int sh = 8 * bw;
-            int t = w / sh, l = w - t * sh;
-            bm = t * 8 + l / bw;
-            bn = first_bn + l % bw;
-        }
-    }
+    block_remap(id, (int)(N / BN), nbm, band, bm, bn);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -211,114 +187,13 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     const int wm = wid / WN, wn = wid % WN;  // wave grid coords (WM x WN)
     const int l15 = lane & 15, l4 = lane >> 4;   // MFMA fragment coords
 
-    // --- LDS: A as [BK][BM] (k-col major), B as [BN][BK] (n-col major) ---
-    __shared__ T sAB[2 * BK * BM + 2 * BN * BK];
-    T* As = sAB;                              // [2][BK][BM]
-    T* Bs = sAB + 2 * BK * BM;                // [2][BN][BK]
+    // --- LDS: two buffers of each operand's tile image (gemm_stage.h) ---
+    __shared__ __align__(16) T sAB[2 * BK * BM + 2 * BN * BK];
+    T* As = sAB;                              // [2][BK * BM]
+    T* Bs = sAB + 2 * BK * BM;                // [2][BN * BK]
 
     const int64_t row0 = (int64_t)bm * BM;    // global row of tile
     const int64_t col0 = (int64_t)bn * BN;    // global col of tile
-
-    constexpr int A_COLS_PER_GLDS = (64 * E) / BM > 0 ? (64 * E) / BM : 1;
-    constexpr int A_GLDS = (BM * sizeof(T) >= 1024)
-        ? (BK * (int)(BM * sizeof(T) / 1024) / NWAVES)
-        : (BK / A_COLS_PER_GLDS / NWAVES);
-    constexpr int B_COLS_PER_GLDS = (64 * E) / BK;
-    constexpr int B_GLDS = BN / B_COLS_PER_GLDS / NWAVES;
-    // B swizzle parameters for fp64: chunk index within a column is
-    // XORed with (c >> BSH) & BMASK (fp32 uses its own masks; see below)
-    constexpr int BMASK = BK / 2 - 1;
-    constexpr int BSH = (BK == 16) ? 1 : 0;
-    using SR = stage_r<T>;
-    using SK = stage_k<T>;
-    static_assert(!(TA || TB) || (BK == 16 && BM == 128 && NWAVES == 4),
-                  "transposed forms exist in the default geometry only");
-    static_assert(!(TA || TB) || (SK::PIECES == A_GLDS && SR::PIECES == B_GLDS),
-                  "both schemes move the same pieces per wave and tile");
-
-    // --- LDS bank-conflict swizzles (measured 8-way on the B-fragment
-    // reads without them — profiles/r01 PMC: conflict cycles were 88% of
-    // LDS cycles). glds forces a lane-linear LDS image, so the
-    // swizzle is applied to the per-lane GLOBAL source address (guide
-    // idiom); both XORs permute 16-byte chunks within one 128-byte global
-    // run, so HBM coalescing is unchanged.
-    //   fp64 A image: column kk stores row-pair i at chunk i ^ (8*(kk&1))
-    //     -> a-read banks: lanes 0-15 distinct, lanes 16-31 shifted by 32.
-    //   fp64 B image: column c stores k-pair p at chunk p ^ ((c>>BSH)&BMASK)
-    //     -> b-read banks: all 32 lanes of a ds_read_b64 group distinct
-    //        (BK=16: column stride 128B; BK=32: column stride 256B).
-    //   fp32 (banks are mod 32 for b32 reads): A chunk ^ 4*(kk&1);
-    //     B chunk ^ (c>>1)&3 -> 2-way worst case (was 8-way).
-    auto issue_tile = [&](int kt, int buf) {
-        const int64_t kbase = (int64_t)kt * BK;
-        if constexpr (TA) {
-            // A^T: A is k x m, runs along k -> scheme K with d = row
-            #pragma unroll
-            for (int i = 0; i < SK::PIECES; i++) {
-                int c = SK::col(wid, i);
-                int d = c + SK::lane_d(lane);
-                const T* g = A + (row0 + d) * lda + kbase + SK::lane_k(lane, d);
-                glds16(g, &As[buf * BK * BM + SK::lds(c)]);
-            }
-        } else
-        if constexpr (BM * sizeof(T) >= 1024) {
-            // >=1 glds per column: chunk q covers column q/CPC, piece q%CPC
-            constexpr int CPC = BM * sizeof(T) / 1024;
-            constexpr int A_CH = BK * CPC / NWAVES;
-            #pragma unroll
-            for (int i = 0; i < A_CH; i++) {
-                int q = wid * A_CH + i;
-                int c = q / CPC, half = q - (q / CPC) * CPC;
-                int lane_row;
-                if constexpr (E == 2)
-                    lane_row = (half * 64 + (lane ^ ((c & 1) << 3))) * E;
-                else
-                    lane_row = (half * (1024 / sizeof(T) / E) * E)
-                               + ((lane ^ ((c & 1) << 2)) * E);
-                const T* g = A + (kbase + c) * lda + row0 + lane_row;
-                glds16(g, &As[buf * BK * BM + c * BM
-                              + half * (int)(1024 / sizeof(T))]);
-            }
-        } else {
-            #pragma unroll
-            for (int i = 0; i < A_GLDS; i++) {
-                int c = (wid * A_GLDS + i) * A_COLS_PER_GLDS;
-                int lane_col = lane / (BM / E);        // 0 or extra col
-                int lane_row;
-                if constexpr (E == 2)
-                    lane_row = (lane ^ (((c + lane_col) & 1) << 3)) * E;
-                else  // f32: 16B chunk XOR 4 by k parity (banks mod 32)
-                    lane_row = ((lane % (BM / E)) ^ (((c + lane_col) & 1) << 2)) * E;
-                const T* g = A + (kbase + c + lane_col) * lda + row0 + lane_row;
-                glds16(g, &As[buf * BK * BM + c * BM]);
-            }
-        }
-        if constexpr (TB) {
-            // B^T: B is n x k, runs along n -> scheme R with d = col
-            #pragma unroll
-            for (int i = 0; i < SR::PIECES; i++) {
-                int c = SR::col(wid, i);
-                int kk = c + SR::lane_k(lane);
-                const T* g = B + (kbase + kk) * ldb + col0 + SR::lane_d(lane, kk);
-                glds16(g, &Bs[buf * BN * BK + SR::lds(c)]);
-            }
-        } else
-        #pragma unroll
-        for (int i = 0; i < B_GLDS; i++) {
-            int c = (wid * B_GLDS + i) * B_COLS_PER_GLDS;
-            int lane_col = lane / (BK / E);
-            int lane_row;
-            if constexpr (E == 2)
-                lane_row = ((lane % (BK / E)) ^ (((c + lane_col) >> BSH) & BMASK)) * E;
-            else if constexpr (E == 4 && BK == 16)
-                // f32: 4 chunks/col; XOR by (c>>1)&3 -> 2-way worst case
-                lane_row = ((lane % 4) ^ (((c + lane_col) >> 1) & 3)) * E;
-            else
-                lane_row = (lane % (BK / E)) * E;
-            const T* g = B + (col0 + c + lane_col) * ldb + kbase + lane_row;
-            glds16(g, &Bs[buf * BN * BK + c * BK]);
-        }
-    };
 
     // C/D row of accumulator element j for this lane (measured per type:
     // tools_dev/debug_mfma.py): f64 16x16x4 is reg-major (l4 + 4j),
@@ -353,43 +228,18 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // sync. Default off (phase_mask 0 = ascending k, reference order).
     const int ph = (phase_mask && (id & phase_mask)) ? (ntiles >> 1) : 0;
 
-    // Pipelined loop's halves of a quad (the two-barrier loop below keeps
-    // its own inline copy so that its code stays what it was): fragments
-    // of quad q (k = 4q .. 4q+3) of the tile staged at At/Bt, undoing the
-    // DMA-side swizzles; then the quad's MT x NT MFMAs.
+    // The halves of a quad: fragments of quad q (k = 4q .. 4q+3) of the
+    // tile staged at At/Bt; then the quad's MT x NT MFMAs.
+    // (s_setprio(1) around the MFMAs measured -5% — not used)
     auto read_quad = [&](const T* At, const T* Bt, int q, T (&a)[MT],
                          T (&b)[NT]) {
         const int kk = q * 4 + l4;
         #pragma unroll
-        for (int mt = 0; mt < MT; mt++) {
-            int rr = wm * (MT * 16) + mt * 16 + l15;
-            if constexpr (TA)
-                a[mt] = At[SK::frag(rr, kk)];
-            else
-            if constexpr (E == 2)
-                a[mt] = At[kk * BM + (((rr >> 1) ^ ((kk & 1) << 3)) << 1)
-                           + (rr & 1)];
-            else
-                a[mt] = At[kk * BM + (((rr >> 2) ^ ((kk & 1) << 2)) << 2)
-                           + (rr & 3)];
-        }
+        for (int mt = 0; mt < MT; mt++)
+            a[mt] = At[SA::frag(wm * (MT * 16) + mt * 16 + l15, kk)];
         #pragma unroll
-        for (int nt = 0; nt < NT; nt++) {
-            int cb = wn * (NT * 16) + nt * 16 + l15;
-            if constexpr (TB)
-                b[nt] = Bt[SR::frag(cb, kk)];
-            else
-            if constexpr (E == 2)
-                b[nt] = Bt[cb * BK
-                           + ((((kk >> 1) ^ ((cb >> BSH) & BMASK)) << 1))
-                           + (kk & 1)];
-            else if constexpr (E == 4 && BK == 16)
-                b[nt] = Bt[cb * BK
-                           + (((kk >> 2) ^ ((cb >> 1) & 3)) << 2)
-                           + (kk & 3)];
-            else
-                b[nt] = Bt[cb * BK + kk];
-        }
+        for (int nt = 0; nt < NT; nt++)
+            b[nt] = Bt[SB::frag(wn * (NT * 16) + nt * 16 + l15, kk)];
     };
     auto mfma_quad = [&](const T (&a)[MT], const T (&b)[NT]) {
         #pragma unroll
@@ -400,6 +250,13 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     };
 
     if constexpr (!PIPE) {
+    auto issue_tile = [&](int kt, int buf) {
+        const int64_t kbase = (int64_t)kt * BK;
+        issue_pieces<SA>((const char*)(A + SA::origin_elems(lda, row0, kbase)),
+                         lda, As, buf * BK * BM, wid, lane);
+        issue_pieces<SB>((const char*)(B + SB::origin_elems(ldb, col0, kbase)),
+                         ldb, Bs, buf * BN * BK, wid, lane);
+    };
     issue_tile(ph, 0);
 
     // Two barriers per k-step with the next tile's DMA issued EARLY and
@@ -413,7 +270,7 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
             if (nxt >= ntiles) nxt -= ntiles;
             issue_tile(nxt, buf ^ 1);
             // our own current-tile DMAs landed; next tile's stay in flight
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_GLDS + B_GLDS) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(P) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -423,53 +280,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         const T* Bt = &Bs[buf * BN * BK];
         #pragma unroll
         for (int q = 0; q < BK / 4; q++) {
-            const int kk = q * 4 + l4;
             T a[MT], b[NT];
-            #pragma unroll
-            for (int mt = 0; mt < MT; mt++) {
-                int rr = wm * (MT * 16) + mt * 16 + l15;
-                if constexpr (TA)
-                    a[mt] = At[SK::frag(rr, kk)];
-                else
-                if constexpr (E == 2)
-                    a[mt] = At[kk * BM + (((rr >> 1) ^ ((kk & 1) << 3)) << 1)
-                               + (rr & 1)];
-                else
-                    a[mt] = At[kk * BM + (((rr >> 2) ^ ((kk & 1) << 2)) << 2)
-                               + (rr & 3)];
-            }
-            #pragma unroll
-            for (int nt = 0; nt < NT; nt++) {
-                int cb = wn * (NT * 16) + nt * 16 + l15;
-                if constexpr (TB)
-                    b[nt] = Bt[SR::frag(cb, kk)];
-                else
-                if constexpr (E == 2)
-                    b[nt] = Bt[cb * BK
-                               + ((((kk >> 1) ^ ((cb >> BSH) & BMASK)) << 1))
-                               + (kk & 1)];
-                else if constexpr (E == 4 && BK == 16)
-                    b[nt] = Bt[cb * BK
-                               + (((kk >> 2) ^ ((cb >> 1) & 3)) << 2)
-                               + (kk & 3)];
-                else
-                    b[nt] = Bt[cb * BK + kk];
-            }
-            // (s_setprio(1) around this block measured -5% — not used)
-            #pragma unroll
-            for (int mt = 0; mt < MT; mt++)
-                #pragma unroll
-                for (int nt = 0; nt < NT; nt++)
-                    acc[mt][nt] = mfma_16x16x4(a[mt], b[nt], acc[mt][nt]);
-#ifdef MARLIN_SCHED_HINT
-            // scheduler hint: interleave next quad's DS reads between
-            // MFMAs, one read per two MFMAs (A/B experiment flag)
-            #pragma unroll
-            for (int g = 0; g < (MT + NT); g++) {
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 DS read
-                __builtin_amdgcn_sched_group_barrier(0x008, (MT * NT) / (MT + NT) + 1, 0);  // MFMAs
-            }
-#endif
+            read_quad(At, Bt, q, a, b);
+            mfma_quad(a, b);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();        // readers done before overwrite
@@ -497,97 +310,44 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // tile per issue and are reset where the MARLIN_GEMM_PHASE rotation
     // wraps. The launcher guarantees the lane offsets fit 32 bits.
     constexpr int Q = BK / 4;
-    constexpr int P = A_GLDS + B_GLDS;       // DMA pieces per wave and tile
     static_assert(Q % 2 == 0, "fragment registers ping-pong per quad");
     const int swid = __builtin_amdgcn_readfirstlane(wid);
-
-    uint32_t a_lane[A_GLDS], b_lane[B_GLDS];     // per-lane byte offsets
-    int64_t a_uni[A_GLDS], b_uni[B_GLDS];        // per-piece uniform offsets
-    int a_lds[A_GLDS], b_lds[B_GLDS];            // LDS element offsets, buf 0
+    // These two loops stay in the kernel body: behind a function, struct
+    // or lambda the same arithmetic gave the steady-state loop another
+    // schedule, and fp64 bk32 measured 0.8% slower
+    // (profiles/r04_stage_refactor.md).
+    uint32_t a_lane[SA::PIECES], b_lane[SB::PIECES];   // per-lane byte offsets
+    int64_t a_uni[SA::PIECES], b_uni[SB::PIECES];      // per-piece uniform offsets
+    int a_lds[SA::PIECES], b_lds[SB::PIECES];          // LDS element offsets
     #pragma unroll
-    for (int i = 0; i < A_GLDS; i++) {
-        if constexpr (TA) {
-            // scheme K on A: what B's pieces are below, with lda for ldb
-            int c = SK::col(swid, i);
-            int d = c + SK::lane_d(lane);
-            a_lane[i] = ((uint32_t)SK::lane_d(lane) * (uint32_t)lda
-                         + (uint32_t)SK::lane_k(lane, d)) * (uint32_t)sizeof(T);
-            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
-            a_lds[i] = SK::lds(c);
-        } else
-        if constexpr (BM * sizeof(T) >= 1024) {
-            constexpr int CPC = BM * sizeof(T) / 1024;
-            int q = swid * A_GLDS + i;
-            int c = q / CPC, half = q - (q / CPC) * CPC;
-            int lane_row;
-            if constexpr (E == 2)
-                lane_row = (half * 64 + (lane ^ ((c & 1) << 3))) * E;
-            else
-                lane_row = (half * (1024 / sizeof(T) / E) * E)
-                           + ((lane ^ ((c & 1) << 2)) * E);
-            a_lane[i] = (uint32_t)lane_row * (uint32_t)sizeof(T);
-            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
-            a_lds[i] = c * BM + half * (int)(1024 / sizeof(T));
-        } else {
-            int c = (swid * A_GLDS + i) * A_COLS_PER_GLDS;
-            int lane_col = lane / (BM / E);        // 0 or extra col
-            int lane_row;
-            if constexpr (E == 2)
-                lane_row = (lane ^ (((c + lane_col) & 1) << 3)) * E;
-            else  // f32: 16B chunk XOR 4 by k parity (banks mod 32)
-                lane_row = ((lane % (BM / E)) ^ (((c + lane_col) & 1) << 2)) * E;
-            a_lane[i] = ((uint32_t)lane_col * (uint32_t)lda
-                         + (uint32_t)lane_row) * (uint32_t)sizeof(T);
-            a_uni[i] = (int64_t)c * lda * (int64_t)sizeof(T);
-            a_lds[i] = c * BM;
-        }
+    for (int i = 0; i < SA::PIECES; i++) {
+        const stage_piece p = SA::piece(swid, i, lane);
+        a_lane[i] = (uint32_t)SA::lane_bytes(p, lda);
+        a_uni[i] = SA::uni_bytes(p, lda);
+        a_lds[i] = p.lds;
     }
     #pragma unroll
-    for (int i = 0; i < B_GLDS; i++) {
-        if constexpr (TB) {
-            // scheme R on B: what A's pieces are above, with ldb for lda
-            int c = SR::col(swid, i);
-            int kk = c + SR::lane_k(lane);
-            b_lane[i] = ((uint32_t)SR::lane_k(lane) * (uint32_t)ldb
-                         + (uint32_t)SR::lane_d(lane, kk)) * (uint32_t)sizeof(T);
-            b_uni[i] = (int64_t)c * ldb * (int64_t)sizeof(T);
-            b_lds[i] = SR::lds(c);
-        } else {
-        int c = (swid * B_GLDS + i) * B_COLS_PER_GLDS;
-        int lane_col = lane / (BK / E);
-        int lane_row;
-        if constexpr (E == 2)
-            lane_row = ((lane % (BK / E)) ^ (((c + lane_col) >> BSH) & BMASK)) * E;
-        else if constexpr (E == 4 && BK == 16)
-            lane_row = ((lane % 4) ^ (((c + lane_col) >> 1) & 3)) * E;
-        else
-            lane_row = (lane % (BK / E)) * E;
-        b_lane[i] = ((uint32_t)lane_col * (uint32_t)ldb
-                     + (uint32_t)lane_row) * (uint32_t)sizeof(T);
-        b_uni[i] = (int64_t)c * ldb * (int64_t)sizeof(T);
-        b_lds[i] = c * BK;
-        }
+    for (int i = 0; i < SB::PIECES; i++) {
+        const stage_piece p = SB::piece(swid, i, lane);
+        b_lane[i] = (uint32_t)SB::lane_bytes(p, ldb);
+        b_uni[i] = SB::uni_bytes(p, ldb);
+        b_lds[i] = p.lds;
     }
 
-    // tile 0 and the per-tile step of each running pointer: an operand
-    // whose runs follow k (B, A^T) starts at its tile's first column and
-    // steps BK elements; one whose runs follow d (A, B^T) starts at its
-    // tile's first row and steps BK columns of its pitch
-    const char* const pA0 = (const char*)(TA ? A + row0 * lda : A + row0);
-    const char* const pB0 = (const char*)(TB ? B + col0 : B + col0 * ldb);
-    const int64_t stepA = TA ? (int64_t)BK * (int64_t)sizeof(T)
-                             : (int64_t)BK * lda * (int64_t)sizeof(T);
-    const int64_t stepB = TB ? (int64_t)BK * ldb * (int64_t)sizeof(T)
-                             : (int64_t)BK * (int64_t)sizeof(T);
+    // tile 0 and the per-tile step of each running pointer
+    const char* const pA0 = (const char*)(A + SA::origin_elems(lda, row0, 0));
+    const char* const pB0 = (const char*)(B + SB::origin_elems(ldb, col0, 0));
+    const int64_t stepA = SA::origin_elems(lda, 0, BK) * (int64_t)sizeof(T);
+    const int64_t stepB = SB::origin_elems(ldb, 0, BK) * (int64_t)sizeof(T);
     const char* pA = pA0 + ph * stepA;       // tile the next issue loads
     const char* pB = pB0 + ph * stepB;
     int kt = ph;
     auto issue_next = [&](int buf) {
         #pragma unroll
-        for (int i = 0; i < A_GLDS; i++)
+        for (int i = 0; i < SA::PIECES; i++)
             glds16(pA + a_uni[i] + a_lane[i], &As[buf * BK * BM + a_lds[i]]);
         #pragma unroll
-        for (int i = 0; i < B_GLDS; i++)
+        for (int i = 0; i < SB::PIECES; i++)
             glds16(pB + b_uni[i] + b_lane[i], &Bs[buf * BN * BK + b_lds[i]]);
         kt++; pA += stepA; pB += stepB;
         if (kt == ntiles) { kt = 0; pA = pA0; pB = pB0; }      // phase wrap
@@ -651,7 +411,58 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     step(s, std::integral_constant<int, 0>{});
     }
 
-    // --- epilogue (row map per type, see above) --------------------------
+    if constexpr (EPI == EPI_TN_ADD) {
+        // Fused transpose/add epilogue (BASELINE config 5): result element
+        // (r, cc) of A*B goes to C[cc + r*ldc] (C is N x M col-major) —
+        // contiguous output runs are (fixed r, varying cc). The store is
+        // staged through LDS in two 64-row half-tiles, laid out
+        // stage[r'*128 + cc], so every global write is a coalesced float4
+        // run (the naive per-element store was 4-byte scattered and cost
+        // ~8% at 40000^2). fp32 on the two-barrier loop only: that loop
+        // leaves the k-loop buffers free behind its closing barrier.
+        static_assert(std::is_same<T, float>::value && !BETA && !PIPE &&
+                      BM == 128 && WM == 2 && WN == 2,
+                      "fused epilogue: fp32 default geometry, two-barrier loop");
+        static_assert(64 * BN == 2 * BK * BM + 2 * BN * BK,
+                      "the 64x128 stage fills the k-loop buffers exactly");
+        float* stage = sAB;                 // k-loop done; reuse the buffers
+        v4f* stage4 = (v4f*)sAB;
+        #pragma unroll
+        for (int half = 0; half < 2; half++) {
+            __builtin_amdgcn_s_barrier();   // prior phase's reads complete
+            if (wm == half) {
+                // this wave pair owns result rows half*64 .. half*64+63
+                #pragma unroll
+                for (int mt = 0; mt < 4; mt++)
+                    #pragma unroll
+                    for (int nt = 0; nt < 4; nt++) {
+                        int rloc = mt * 16 + l4 * 4;      // 0..63
+                        int cc = wn * 64 + nt * 16 + l15;
+                        #pragma unroll
+                        for (int j = 0; j < 4; j++)
+                            stage[(rloc + j) * BN + cc] = acc[mt][nt][j];
+                    }
+            }
+            __builtin_amdgcn_s_barrier();
+            // 64 rows x 32 float4 = 2048 stores over 256 threads
+            #pragma unroll
+            for (int i = 0; i < 8; i++) {
+                int idx = tid + i * 256;
+                int rloc = idx >> 5;                      // 0..63
+                int q = idx & 31;                         // float4 index in row
+                int64_t r = row0 + half * 64 + rloc;
+                int64_t off = col0 + 4 * q + r * ldc;
+                v4f v = stage4[rloc * (BN / 4) + q];
+                if (addC) {
+                    const v4f* ap = (const v4f*)(addC + off);
+                    v4f av = *ap;
+                    v.x += av.x; v.y += av.y; v.z += av.z; v.w += av.w;
+                }
+                *(v4f*)(C + off) = v;
+            }
+        }
+    } else {
+    // --- plain store (row map per type, see above) -----------------------
     #pragma unroll
     for (int mt = 0; mt < MT; mt++)
         #pragma unroll
@@ -662,168 +473,9 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
             #pragma unroll
             for (int j = 0; j < 4; j++) cp[rstep * j] = acc[mt][nt][j];
         }
-}
-
-// fp32 GEMM with fused transpose/add epilogue (BASELINE config 5):
-// C_out[n x m] = (A*B)^T (+ addC). Same main loop as the sgemm config
-// (incl. the f32 XOR swizzles and the supertiled band remap); the
-// transposed store is staged through LDS in two 64-row half-tiles so
-// every global write is a coalesced float4 run (the naive per-element
-// store was 4-byte scattered and cost ~8% at 40000^2).
-__launch_bounds__(256, 2)
-__global__ void sgemm_mfma_tn_epilogue_kernel(
-        int64_t M, int64_t N, int64_t K,
-        const float* __restrict__ A, int64_t lda,
-        const float* __restrict__ B, int64_t ldb,
-        float* __restrict__ C, int64_t ldc,      // C is N x M col-major
-        const float* __restrict__ addC,          // N x M or nullptr
-        int nbm, int band) {
-    constexpr int BM = 128, BN = 128, BK = 16;
-    // supertiled band remap (same as gemm_mfma_kernel: the 8 blocks on
-    // one XCD share a B tile column and a contiguous A panel in L2)
-    int id = blockIdx.x;
-    int bn, bm;
-    {
-        int nbn = (int)(N / BN);
-        int per_band = nbm * band;
-        int b0 = id / per_band;
-        int w = id - b0 * per_band;
-        int first_bn = b0 * band;
-        int bw = min(band, nbn - first_bn);
-        int sh = 8 * bw;
-        int t = w / sh, l = w - t * sh;
-        bm = t * 8 + l / bw;
-        bn = first_bn + l % bw;
-    }
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int l15 = lane & 15, l4 = lane >> 4;
-
-    __shared__ __align__(16) float sAB[2 * BK * BM + 2 * BN * BK];
-    float* As = sAB;
-    float* Bs = sAB + 2 * BK * BM;
-    const int64_t row0 = (int64_t)bm * BM;
-    const int64_t col0 = (int64_t)bn * BN;
-
-    constexpr int E = 4;
-    constexpr int A_COLS_PER_GLDS = (64 * E) / BM;
-    constexpr int A_GLDS = BK / A_COLS_PER_GLDS / 4;
-    constexpr int B_COLS_PER_GLDS = (64 * E) / BK;
-    constexpr int B_GLDS = BN / B_COLS_PER_GLDS / 4;
-
-    // f32 XOR swizzles on the GLOBAL source address (same as the sgemm
-    // config of gemm_mfma_kernel: A chunk ^4 by k parity, B chunk
-    // ^(c>>1)&3 — banks are mod 32 for b32 reads)
-    auto issue_tile = [&](int kt, int buf) {
-        const int64_t kbase = (int64_t)kt * BK;
-        #pragma unroll
-        for (int i = 0; i < A_GLDS; i++) {
-            int c = (wid * A_GLDS + i) * A_COLS_PER_GLDS;
-            int lane_col = lane / (BM / E);
-            int lane_row = ((lane % (BM / E)) ^ (((c + lane_col) & 1) << 2))
-                           * E;
-            glds16(A + (kbase + c + lane_col) * lda + row0 + lane_row,
-                   &As[buf * BK * BM + c * BM]);
-        }
-        #pragma unroll
-        for (int i = 0; i < B_GLDS; i++) {
-            int c = (wid * B_GLDS + i) * B_COLS_PER_GLDS;
-            int lane_col = lane / (BK / E);
-            int lane_row = ((lane % 4) ^ (((c + lane_col) >> 1) & 3)) * E;
-            glds16(B + (col0 + c + lane_col) * ldb + kbase + lane_row,
-                   &Bs[buf * BN * BK + c * BK]);
-        }
-    };
-
-    v4f acc[4][4];
-    #pragma unroll
-    for (int mt = 0; mt < 4; mt++)
-        #pragma unroll
-        for (int nt = 0; nt < 4; nt++) acc[mt][nt] = v4f{0};
-
-    const int ntiles = (int)(K / BK);
-    issue_tile(0, 0);
-    for (int kt = 0; kt < ntiles; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < ntiles) {
-            issue_tile(kt + 1, buf ^ 1);
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_GLDS + B_GLDS) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        const float* At = &As[buf * BK * BM];
-        const float* Bt = &Bs[buf * BN * BK];
-        #pragma unroll
-        for (int q = 0; q < BK / 4; q++) {
-            const int kk = q * 4 + l4;
-            float a[4], b[4];
-            #pragma unroll
-            for (int mt = 0; mt < 4; mt++) {
-                int rr = wm * 64 + mt * 16 + l15;
-                a[mt] = At[kk * BM + (((rr >> 2) ^ ((kk & 1) << 2)) << 2)
-                           + (rr & 3)];
-            }
-            #pragma unroll
-            for (int nt = 0; nt < 4; nt++) {
-                int cb = wn * 64 + nt * 16 + l15;
-                b[nt] = Bt[cb * BK + (((kk >> 2) ^ ((cb >> 1) & 3)) << 2)
-                           + (kk & 3)];
-            }
-            #pragma unroll
-            for (int mt = 0; mt < 4; mt++)
-                #pragma unroll
-                for (int nt = 0; nt < 4; nt++)
-                    acc[mt][nt] = mfma_16x16x4(a[mt], b[nt], acc[mt][nt]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-
-    // Transposed store via LDS: result element (r, cc) of A*B goes to
-    // C[cc + r*ldc] — contiguous output runs are (fixed r, varying cc).
-    // Stage 64 result rows at a time into sAB (exactly 64x128 floats),
-    // laid out stage[r'*128 + cc], then write float4 runs cooperatively.
-    float* stage = sAB;                 // k-loop done; reuse the buffers
-    v4f* stage4 = (v4f*)sAB;
-    #pragma unroll
-    for (int half = 0; half < 2; half++) {
-        __builtin_amdgcn_s_barrier();   // prior phase's reads complete
-        if (wm == half) {
-            // this wave pair owns result rows half*64 .. half*64+63
-            #pragma unroll
-            for (int mt = 0; mt < 4; mt++)
-                #pragma unroll
-                for (int nt = 0; nt < 4; nt++) {
-                    int rloc = mt * 16 + l4 * 4;      // 0..63
-                    int cc = wn * 64 + nt * 16 + l15;
-                    #pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        stage[(rloc + j) * BN + cc] = acc[mt][nt][j];
-                }
-        }
-        __builtin_amdgcn_s_barrier();
-        // 64 rows x 32 float4 = 2048 stores over 256 threads
-        #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int idx = tid + i * 256;
-            int rloc = idx >> 5;                      // 0..63
-            int q = idx & 31;                         // float4 index in row
-            int64_t r = row0 + half * 64 + rloc;
-            int64_t off = col0 + 4 * q + r * ldc;
-            v4f v = stage4[rloc * (BN / 4) + q];
-            if (addC) {
-                const v4f* ap = (const v4f*)(addC + off);
-                v4f av = *ap;
-                v.x += av.x; v.y += av.y; v.z += av.z; v.w += av.w;
-            }
-            *(v4f*)(C + off) = v;
-        }
     }
 }
+
 
 // ---------------------------------------------------------------------------
 // Deterministic synthetic input fill: splitmix64 of (seed + (idx+1)*gamma),
@@ -1003,18 +655,57 @@ __global__ void gemv_reduce_kernel(int64_t m, int nchunks,
 }
 
 // ---------------------------------------------------------------------------
+// What mxk_gemm last launched (mx_last_gemm_config): the env knobs of
+// mxk_gemm_op are latched per process, so a test can only prove which
+// instantiation it exercised by reading this record back.
+static mx_gemm_cfg_t g_last_gemm_cfg = {};
+// k-loop of that launch (mx_last_gemm_loop): 0 = two-barrier, 1 = pipelined
+static int g_last_gemm_loop = 0;
+// op(A), op(B) of that launch (mx_last_gemm_op): 1 = transposed
+static int g_last_gemm_op[2] = {0, 0};
+
+// The runtime half of a GEMM launch; the template arguments of launch_gemm
+// are the compile-time half.
+struct gemm_call {
+    int64_t M, N, K;
+    const void* A; int64_t lda;
+    const void* B; int64_t ldb;
+    void* C; int64_t ldc;
+    int band, phase_mask;
+    int loopsel;            // MARLIN_GEMM_LOOP: 0 twobar, 1 pipe, -1 unset
+    bool pitch32;           // the pipelined loop's 32-bit lane offsets fit
+    hipStream_t stream;
+};
+
+// Picks the k-loop, launches that instantiation, records what it launched.
+template <typename T, int BETA, int BK, int BM, int WM, int WN,
+          int TA = 0, int TB = 0>
+static void launch_gemm(const gemm_call& g) {
+    const bool pipe = g.pitch32 && (g.loopsel >= 0 ? g.loopsel == 1
+                                    : !(sizeof(T) == 4 && BK == 16));
+    g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(T) == 4, BETA, BK, BM, WM * WN,
+                                    g.band, g.phase_mask};
+    g_last_gemm_loop = pipe ? 1 : 0;
+    g_last_gemm_op[0] = TA;
+    g_last_gemm_op[1] = TB;
+    auto go = [&](auto pipe_c) {
+        hipLaunchKernelGGL(
+            (gemm_mfma_kernel<T, BETA, BK, BM, WM, WN, decltype(pipe_c)::value,
+                              TA, TB>),
+            dim3((unsigned)((g.M / BM) * (g.N / 128))), dim3(WM * WN * 64),
+            0, g.stream, g.M, g.N, g.K, (const T*)g.A, g.lda,
+            (const T*)g.B, g.ldb, (T*)g.C, g.ldc, (int)(g.M / BM), g.band,
+            g.phase_mask, (const T*)nullptr);
+    };
+    if (pipe) go(std::integral_constant<int, 1>{});
+    else      go(std::integral_constant<int, 0>{});
+}
+
+// ---------------------------------------------------------------------------
 // C-visible launchers (called from marlin_gpu.cpp).
 extern "C" {
 
-// What mxk_gemm last launched (mx_last_gemm_config): the env knobs below
-// are latched per process, so a test can only prove which instantiation
-// it exercised by reading this record back.
-static mx_gemm_cfg_t g_last_gemm_cfg = {};
-
 void mxk_last_gemm_config(mx_gemm_cfg_t* out) { *out = g_last_gemm_cfg; }
-
-// k-loop of that launch (mx_last_gemm_loop): 0 = two-barrier, 1 = pipelined
-static int g_last_gemm_loop = 0;
 
 void mxk_last_gemm_loop(int* out) { *out = g_last_gemm_loop; }
 
@@ -1024,9 +715,6 @@ void mxk_last_gemm_loop(int* out) { *out = g_last_gemm_loop; }
 static inline bool pitch_ok(int64_t ld, int64_t rows, int64_t elems16) {
     return ld >= rows && ld % elems16 == 0;
 }
-
-// op(A), op(B) of that launch (mx_last_gemm_op): 1 = transposed
-static int g_last_gemm_op[2] = {0, 0};
 
 void mxk_last_gemm_op(int* trans_a, int* trans_b) {
     *trans_a = g_last_gemm_op[0];
@@ -1087,65 +775,35 @@ int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
     // keeps the two-barrier loop. MARLIN_GEMM_LOOP=twobar / =pipe force
     // one loop everywhere (paired comparisons, tests). A pitch so large
     // that the pipelined loop's 32-bit per-lane DMA offsets (up to 15
-    // columns of B, 1 of A, plus one 1 KiB run) could overflow always
-    // takes the two-barrier loop. A transposed operand takes the other
+    // columns of B, 1 of A, plus one 1 KiB run; checked at the largest
+    // admitted pitch by tests/test_gemm_stage_layout.py) could overflow
+    // always takes the two-barrier loop. A transposed operand takes the other
     // operand's offsets with its own pitch, so the one bound on both
     // pitches covers every form.
     static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
     const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
                       : loopenv[0] == 'p' ? 1 : -1;
     const bool pitch32 = lda < ((int64_t)1 << 26) && ldb < ((int64_t)1 << 26);
-    #define LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, PIPE, TA, TB)         \
-        hipLaunchKernelGGL(                                                \
-            (gemm_mfma_kernel<TY, BETA, BK, BMv, WMv, WNv, PIPE, TA, TB>), \
-            dim3((unsigned)((M / BMv) * nbn)), dim3(WMv * WNv * 64), 0,    \
-            stream, M, N, K, (const TY*)A, lda, (const TY*)B, ldb, (TY*)C, \
-            ldc, (int)(M / BMv), band, phase_mask)
-    #define LAUNCH_OP(TY, BETA, BK, BMv, WMv, WNv, TA, TB)                 \
-        do {                                                               \
-        g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(TY) == 4, BETA, BK, BMv,    \
-                                        WMv * WNv, band, phase_mask};      \
-        const bool pipe = pitch32 && (loopsel >= 0 ? loopsel == 1          \
-                              : !(sizeof(TY) == 4 && BK == 16));           \
-        g_last_gemm_loop = pipe ? 1 : 0;                                   \
-        g_last_gemm_op[0] = TA;                                            \
-        g_last_gemm_op[1] = TB;                                            \
-        if (pipe) LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 1, TA, TB);     \
-        else      LAUNCH_LOOP(TY, BETA, BK, BMv, WMv, WNv, 0, TA, TB);     \
-        } while (0)
-    #define LAUNCH(TY, BETA, BK, BMv, WMv, WNv)                            \
-        LAUNCH_OP(TY, BETA, BK, BMv, WMv, WNv, 0, 0)
-    // transposed forms: default geometry, per type and beta
-    #define LAUNCH_T(TY, TA, TB)                                           \
-        do {                                                               \
-        if (beta_one) LAUNCH_OP(TY, 1, 16, 128, 2, 2, TA, TB);             \
-        else          LAUNCH_OP(TY, 0, 16, 128, 2, 2, TA, TB);             \
-        } while (0)
-    if (trans_a || trans_b) {
-        if (is_fp32) {
-            if (trans_a && trans_b) LAUNCH_T(float, 1, 1);
-            else if (trans_a)       LAUNCH_T(float, 1, 0);
-            else                    LAUNCH_T(float, 0, 1);
-        } else {
-            if (trans_a && trans_b) LAUNCH_T(double, 1, 1);
-            else if (trans_a)       LAUNCH_T(double, 1, 0);
-            else                    LAUNCH_T(double, 0, 1);
+    const gemm_call g{M, N, K, A, lda, B, ldb, C, ldc, band, phase_mask,
+                      loopsel, pitch32, stream};
+    // form and geometry, per type and beta: the transposed forms exist in
+    // the default geometry only, bm256 for fp64 only (never set for fp32)
+    auto dispatch = [&](auto t, auto beta) {
+        using T = decltype(t);
+        constexpr int BT = decltype(beta)::value;
+        if (trans_a && trans_b) launch_gemm<T, BT, 16, 128, 2, 2, 1, 1>(g);
+        else if (trans_a)       launch_gemm<T, BT, 16, 128, 2, 2, 1, 0>(g);
+        else if (trans_b)       launch_gemm<T, BT, 16, 128, 2, 2, 0, 1>(g);
+        else if (bm256) {
+            if constexpr (sizeof(T) == 8) launch_gemm<T, BT, 16, 256, 4, 2>(g);
         }
-    } else
-    if (is_fp32) {
-        if (beta_one) { if (bk32) LAUNCH(float, 1, 32, 128, 2, 4); else LAUNCH(float, 1, 16, 128, 2, 2); }
-        else          { if (bk32) LAUNCH(float, 0, 32, 128, 2, 4); else LAUNCH(float, 0, 16, 128, 2, 2); }
-    } else if (bm256) {
-        if (beta_one) LAUNCH(double, 1, 16, 256, 4, 2);
-        else          LAUNCH(double, 0, 16, 256, 4, 2);
-    } else {
-        if (beta_one) { if (bk32) LAUNCH(double, 1, 32, 128, 2, 4); else LAUNCH(double, 1, 16, 128, 2, 2); }
-        else          { if (bk32) LAUNCH(double, 0, 32, 128, 2, 4); else LAUNCH(double, 0, 16, 128, 2, 2); }
-    }
-    #undef LAUNCH_T
-    #undef LAUNCH_OP
-    #undef LAUNCH
-    #undef LAUNCH_LOOP
+        else if (bk32)          launch_gemm<T, BT, 32, 128, 2, 4>(g);
+        else                    launch_gemm<T, BT, 16, 128, 2, 2>(g);
+    };
+    using one = std::integral_constant<int, 1>;
+    using zero = std::integral_constant<int, 0>;
+    if (is_fp32) { if (beta_one) dispatch(float{}, one{}); else dispatch(float{}, zero{}); }
+    else         { if (beta_one) dispatch(double{}, one{}); else dispatch(double{}, zero{}); }
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 
@@ -1172,8 +830,12 @@ int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K,
     int nbm = (int)(M / 128), nbn = (int)(N / 128);
     int band = nbn < 8 ? nbn : 8;
     dim3 grid((unsigned)(nbm * nbn)), block(256);
-    hipLaunchKernelGGL(sgemm_mfma_tn_epilogue_kernel, grid, block, 0, stream,
-                       M, N, K, A, lda, B, ldb, C, ldc, addC, nbm, band);
+    // the fp32 default geometry on the two-barrier loop, supertiled bands,
+    // no k-phase stagger, whatever the MARLIN_GEMM_* knobs say
+    hipLaunchKernelGGL(
+        (gemm_mfma_kernel<float, 0, 16, 128, 2, 2, 0, 0, 0, EPI_TN_ADD>),
+        grid, block, 0, stream, M, N, K, A, lda, B, ldb, C, ldc, nbm, band,
+        0, addC);
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 
