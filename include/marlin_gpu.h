@@ -230,6 +230,55 @@ int mx_gemm_device_op(mx_ctx* ctx, int is_fp32, int beta_one, int trans_a,
  * before the first launch) */
 int mx_last_gemm_op(mx_ctx* ctx, int* trans_a, int* trans_b);
 
+/* Grouped GEMM: count independent products C_i (+)= op(A_i)·op(B_i) in ONE
+ * kernel launch whose grid is the union of all their 128x128 C tiles, so
+ * many small products fill the GPU the way one large one does. Type,
+ * beta_one and the op form are uniform per call; shapes, pitches, buffers
+ * and element offsets into the buffers are per problem. Each C tile runs
+ * the k-loop the plain entry runs, so the result of a problem is
+ * bit-identical to mx_gemm_device_op on that problem alone.
+ *
+ * Per problem the pitch contract is that of mx_gemm_device_op (m, n
+ * multiples of 128, k of 16; the trans_* meaning of lda / ldb), and each
+ * offset times the element size is a multiple of 16 bytes.
+ *
+ * The WHOLE table is validated before anything is enqueued; a violation
+ * returns MX_EINVAL and touches no buffer. Refused: a contract violation,
+ * a NULL buffer in a non-empty problem, a region that does not fit its
+ * buffer (off + (cols-1)*ld + rows elements), count < 0, NULL problems
+ * with count > 0, a trans_* outside {0,1}, and aliasing: every C region
+ * must be disjoint from every other problem's C region and from every A
+ * and B region of the call. Two regions of one buffer are disjoint only
+ * when their byte spans are, or when their pitches are equal and they are
+ * disjoint rectangles (rows off % ld .. +rows, columns off / ld .. +cols,
+ * with off % ld + rows <= ld). A and B regions may repeat and overlap
+ * freely (one panel feeding a row of updates; dA == dB, the Gram form).
+ *
+ * A problem with m == 0 or n == 0 is skipped; k == 0 zeroes the C region
+ * when beta_one == 0 and leaves it alone otherwise; count == 0, or a call
+ * with nothing left to launch, returns MX_OK and launches no kernel.
+ *
+ * The default kernel geometry only (bk 16, bm 128, 4 waves), as for the
+ * transposed forms: MARLIN_GEMM_CFG is ignored, MARLIN_GEMM_LOOP is
+ * honoured (default: fp64 pipelined, fp32 two-barrier; one pitch of 2^26
+ * elements or more puts the whole launch on the two-barrier loop),
+ * MARLIN_GEMM_BAND and _REMAP apply per problem, _PHASE is not applied.
+ * Stats: flops = sum of 2mkn, gemm_ms = event time of the one launch,
+ * gemm_launches = 1 (0 when nothing launched). mx_last_gemm_config (band
+ * = that of the first table entry), _op and _loop report the launch. */
+typedef struct {
+  int64_t m, k, n;        /* dims of the product, padded: m, n % 128 == 0, k % 16 == 0 */
+  const mx_dbuf* dA; int64_t a_off, lda;   /* offsets and pitches in elements */
+  const mx_dbuf* dB; int64_t b_off, ldb;
+  mx_dbuf*       dC; int64_t c_off, ldc;
+} mx_gemm_problem_t;
+int mx_gemm_device_grouped(mx_ctx* ctx, int is_fp32, int beta_one,
+                           int trans_a, int trans_b, int count,
+                           const mx_gemm_problem_t* problems);
+/* Problems that reached the kernel and grid size (blocks) of the most
+ * recent grouped launch in this process; zeros before the first. */
+int mx_last_gemm_group(mx_ctx* ctx, int* problems_launched, int64_t* blocks);
+
 /* Introspection: the gemm_mfma_kernel instantiation and remap arguments
  * of the most recent plain GEMM launch in this process (any entry that
  * reaches the kernel launcher; all zero before the first launch). The

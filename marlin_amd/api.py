@@ -247,15 +247,17 @@ class DenseVecMatrix:
         from .io import save_matrix_file
         save_matrix_file(self, path)
 
-    def luDecompose(self, mode="auto", base_size=1000):
-        """DenseVecMatrix.luDecompose (DenseVecMatrix.scala:283-464)."""
+    def luDecompose(self, mode="auto", base_size=1000, grouped=True):
+        """DenseVecMatrix.luDecompose (DenseVecMatrix.scala:283-464).
+        grouped=False keeps one launch per block product (same bits)."""
         from .linalg import lu_decompose
-        return lu_decompose(self, mode, base_size)
+        return lu_decompose(self, mode, base_size, grouped)
 
-    def inverse(self, mode="auto", base_size=1000):
-        """DenseVecMatrix.inverse (DenseVecMatrix.scala:565-764)."""
+    def inverse(self, mode="auto", base_size=1000, grouped=True):
+        """DenseVecMatrix.inverse (DenseVecMatrix.scala:565-764).
+        grouped=False keeps one launch per block product (same bits)."""
         from .linalg import inverse
-        return inverse(self, mode, base_size)
+        return inverse(self, mode, base_size, grouped)
 
     def lr(self, step_size, iters):
         """DenseVecMatrix.lr (DenseVecMatrix.scala:1005-1035): SGD
@@ -298,10 +300,11 @@ class DenseVecMatrix:
             d.free()
         return out
 
-    def choleskyDecompose(self, mode="auto", base_size=1000):
-        """DenseVecMatrix.choleskyDecompose (DenseVecMatrix.scala:475-566)."""
+    def choleskyDecompose(self, mode="auto", base_size=1000, grouped=True):
+        """DenseVecMatrix.choleskyDecompose (DenseVecMatrix.scala:475-566).
+        grouped=False keeps one launch per block product (same bits)."""
         from .linalg import cholesky_decompose
-        return cholesky_decompose(self, mode, base_size)
+        return cholesky_decompose(self, mode, base_size, grouped)
 
     def toBreeze(self):
         return self._host().copy()
@@ -356,7 +359,9 @@ class BlockMatrix:
         """BlockMatrix.multiply (BlockMatrix.scala:149-220). The reference
         re-shuffles (emit x n / x m, join, reduceByKey); the engine computes
         the same per-C-tile sums with one owner per tile, so only the
-        per-tile GEMM-accumulate chain remains (mx_tile_dgemm_acc)."""
+        per-tile GEMM-accumulate chain remains: every block of both
+        operands is uploaded once, and step l of all the chains is one
+        grouped launch (Engine.gemm_grouped)."""
         if isinstance(other, (int, float)):
             return self._ew1("muls", other)
         if isinstance(other, np.ndarray) and other.ndim == 1:
@@ -393,6 +398,31 @@ class BlockMatrix:
             # reference re-slices (BlockMatrix.scala:187-216); we re-block
             other = _to_block(other.toBreeze(), self.numBlksByCol(),
                               other.numBlksByCol(), self._eng)
+        eng = self._engine()
+        ks = self.numBlksByCol()
+        ij = [(i, j) for i in range(self.numBlksByRow())
+              for j in range(other.numBlksByCol())]
+        dA = {k: eng.upload_matrix(v) for k, v in self._blocks.items()}
+        dB = {k: eng.upload_matrix(v) for k, v in other._blocks.items()}
+        dC = [None] * len(ij)
+        try:
+            for l in range(ks):
+                dC = eng.gemm_grouped(
+                    [(dA[(i, l)], dB[(l, j)], c) for (i, j), c in zip(ij, dC)],
+                    accumulate=l > 0)
+            out = {k: eng.download_matrix(c) for k, c in zip(ij, dC)}
+        finally:
+            for d in list(dA.values()) + list(dB.values()) + dC:
+                if d is not None:
+                    d.free()
+        return BlockMatrix(out, self.numRows(), other.numCols(),
+                           engine=self._eng)
+
+    def _multiply_tile_chain(self, other):
+        """The per-product form of multiply(BlockMatrix): one
+        mx_tile_dgemm_acc per (i, j, l) on host tiles. Same block grids
+        required. Kept as the comparison arm of the grouped path (tests,
+        tools_dev/bench_gemm_grouped.py); the results are bit-equal."""
         eng = self._engine()
         ks = self.numBlksByCol()
         out = {}

@@ -24,6 +24,9 @@
 //     geometry and operand form; both loops go through it. The fused
 //     transpose/add epilogue of config 5 is the EPI parameter of the one
 //     GEMM template.
+//   - Many small products run as ONE launch over the union of their tiles
+//     (GRP parameter of the same template, table of gemm_group_plan.h):
+//     a block finds its problem in the prologue, then runs the same code.
 //   - All matrices COLUMN-MAJOR with padded leading dims (multiples of the
 //     tile) — the host pads, so the kernel has no edge paths.
 //   - Grid is remapped into column bands so the ~512 resident blocks share
@@ -39,6 +42,7 @@
 #include <type_traits>
 
 #include "../../include/marlin_gpu.h"   // mx_gemm_cfg_t
+#include "gemm_group_plan.h"            // mx_group_entry (the device table)
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -68,6 +72,24 @@ DEVFN void glds16(const void* g, void* lds) {
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) uint32_t*)g,
         (__attribute__((address_space(3))) uint32_t*)lds, 16, 0, 0);
+}
+
+// Block-uniform loads of the grouped table: the value is the same in every
+// lane, and readfirstlane says so, which keeps it in scalar registers.
+DEVFN int32_t sload(const int32_t* p) {
+    return __builtin_amdgcn_readfirstlane(*p);
+}
+DEVFN int64_t sload(const int64_t* p) {
+    const int64_t v = *p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+DEVFN const void* sload_ptr(const void* const* p) {
+    return (const void*)(uintptr_t)sload((const int64_t*)p);
+}
+DEVFN void* sload_ptr(void* const* p) {
+    return (void*)(uintptr_t)sload((const int64_t*)p);
 }
 
 // The LDS staging layout (schemes R and K: DMA source per lane, LDS image,
@@ -155,17 +177,25 @@ DEVFN void block_remap(int id, int nbn, int nbm, int band, int& bm, int& bn) {
 // C_out[n x m] = (A*B)^T (+ addC) — see the end of the kernel.
 enum { EPI_STORE = 0, EPI_TN_ADD = 1 };
 
+// GRP = 1 is the grouped launch (mx_gemm_device_grouped): the grid is the
+// union of the tiles of many problems and `grp` is the device table of
+// gemm_group_plan.h (entries, then tile_start); the per-launch scalars are
+// unused but for nbm_, which carries the entry count. The prologue finds
+// the block's problem, loads its descriptor and takes the problem-local
+// block id; from there the code below runs unchanged on that problem's
+// A, lda, B, ldb, C, ldc, ntiles. Default geometry only, phase 0.
 template <typename T, int BETA, int BK, int BM, int WM, int WN, int PIPE,
-          int TA = 0, int TB = 0, int EPI = EPI_STORE>
+          int TA = 0, int TB = 0, int EPI = EPI_STORE, int GRP = 0>
 __launch_bounds__(WM * WN * 64, 2)
 __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
-                                 const T* __restrict__ A, int64_t lda,
-                                 const T* __restrict__ B, int64_t ldb,
-                                 T* __restrict__ C, int64_t ldc,
-                                 int nbm /* grid rows = M/BM */,
-                                 int band /* column-band width in blocks */,
+                                 const T* __restrict__ A_, int64_t lda_,
+                                 const T* __restrict__ B_, int64_t ldb_,
+                                 T* __restrict__ C_, int64_t ldc_,
+                                 int nbm_ /* grid rows = M/BM */,
+                                 int band_ /* column-band width in blocks */,
                                  int phase_mask /* k-phase stagger mask */,
-                                 const T* __restrict__ addC /* EPI_TN_ADD */) {
+                                 const T* __restrict__ addC /* EPI_TN_ADD */,
+                                 const mx_group_entry* __restrict__ grp) {
     constexpr int BN = 128;
     constexpr int NWAVES = WM * WN;
     constexpr int MT = (BM / WM) / 16;      // 16x16 frags per wave, m
@@ -177,9 +207,36 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
                                            stage_k<T, BN, BK, NWAVES>>;
     constexpr int P = SA::PIECES + SB::PIECES;   // DMA pieces per wave, tile
 
-    const int id = blockIdx.x;
+    const T* __restrict__ A = A_;
+    const T* __restrict__ B = B_;
+    T* __restrict__ C = C_;
+    int64_t lda = lda_, ldb = ldb_, ldc = ldc_;
+    int nbm = nbm_, nbn = (int)(N / BN), band = band_;
+    int grp_ntiles = 0;
+    int id = blockIdx.x;
+    if constexpr (GRP != 0) {
+        static_assert(BK == 16 && BM == 128 && WM == 2 && WN == 2 &&
+                      EPI == EPI_STORE, "grouped: default geometry only");
+        // wave-uniform binary search of tile_start (count + 1 entries
+        // behind the descriptors) for the problem owning this block
+        const int count = nbm_;
+        const int32_t* __restrict__ tile_start = (const int32_t*)(grp + count);
+        int lo = 0, hi = count - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (sload(&tile_start[mid]) <= id) lo = mid; else hi = mid - 1;
+        }
+        const mx_group_entry* __restrict__ e = grp + lo;
+        A = (const T*)sload_ptr(&e->A);
+        B = (const T*)sload_ptr(&e->B);
+        C = (T*)sload_ptr(&e->C);
+        lda = sload(&e->lda); ldb = sload(&e->ldb); ldc = sload(&e->ldc);
+        grp_ntiles = sload(&e->ntiles);
+        nbm = sload(&e->nbm); nbn = sload(&e->nbn); band = sload(&e->band);
+        id -= sload(&tile_start[lo]);
+    }
     int bn, bm;
-    block_remap(id, (int)(N / BN), nbm, band, bm, bn);
+    block_remap(id, nbn, nbm, band, bm, bn);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -220,7 +277,7 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
             for (int nt = 0; nt < NT; nt++) acc[mt][nt] = ACC{0};
     }
 
-    const int ntiles = (int)(K / BK);
+    const int ntiles = GRP != 0 ? grp_ntiles : (int)(K / BK);
     // k-phase stagger experiment (MARLIN_GEMM_PHASE): blocks matching
     // the mask start their k-loop half-way round (accumulation order
     // rotated per tile — still deterministic run-to-run), so the two
@@ -695,7 +752,39 @@ static void launch_gemm(const gemm_call& g) {
             dim3((unsigned)((g.M / BM) * (g.N / 128))), dim3(WM * WN * 64),
             0, g.stream, g.M, g.N, g.K, (const T*)g.A, g.lda,
             (const T*)g.B, g.ldb, (T*)g.C, g.ldc, (int)(g.M / BM), g.band,
-            g.phase_mask, (const T*)nullptr);
+            g.phase_mask, (const T*)nullptr,
+            (const mx_group_entry*)nullptr);
+    };
+    if (pipe) go(std::integral_constant<int, 1>{});
+    else      go(std::integral_constant<int, 0>{});
+}
+
+// problems and blocks of the last grouped launch (mx_last_gemm_group)
+static int g_last_gemm_group_problems = 0;
+static int64_t g_last_gemm_group_blocks = 0;
+
+// The grouped launch of one (type, beta, form): the default geometry, the
+// k-loop chosen as launch_gemm chooses it, phase 0.
+template <typename T, int BETA, int TA, int TB>
+static void launch_gemm_grouped(int count, unsigned blocks, int band0,
+                                const mx_group_entry* table, int loopsel,
+                                bool pitch32, hipStream_t stream) {
+    const bool pipe = pitch32 && (loopsel >= 0 ? loopsel == 1
+                                  : sizeof(T) != 4);
+    g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(T) == 4, BETA, 16, 128, 4, band0, 0};
+    g_last_gemm_loop = pipe ? 1 : 0;
+    g_last_gemm_op[0] = TA;
+    g_last_gemm_op[1] = TB;
+    g_last_gemm_group_problems = count;
+    g_last_gemm_group_blocks = blocks;
+    auto go = [&](auto pipe_c) {
+        hipLaunchKernelGGL(
+            (gemm_mfma_kernel<T, BETA, 16, 128, 2, 2, decltype(pipe_c)::value,
+                              TA, TB, EPI_STORE, 1>),
+            dim3(blocks), dim3(256), 0, stream, (int64_t)0, (int64_t)0,
+            (int64_t)0, (const T*)nullptr, (int64_t)0, (const T*)nullptr,
+            (int64_t)0, (T*)nullptr, (int64_t)0, count, 0, 0,
+            (const T*)nullptr, table);
     };
     if (pipe) go(std::integral_constant<int, 1>{});
     else      go(std::integral_constant<int, 0>{});
@@ -704,6 +793,67 @@ static void launch_gemm(const gemm_call& g) {
 // ---------------------------------------------------------------------------
 // C-visible launchers (called from marlin_gpu.cpp).
 extern "C" {
+
+// The latched remap knobs the grouped plan needs: MARLIN_GEMM_BAND width
+// (>= 1) and whether MARLIN_GEMM_REMAP=bands asks for plain bands.
+void mxk_gemm_remap_knobs(int* band_width, int* plain_bands) {
+    static const char* bandenv = getenv("MARLIN_GEMM_BAND");
+    static const char* remap = getenv("MARLIN_GEMM_REMAP");
+    int bandw = bandenv ? atoi(bandenv) : 8;
+    *band_width = bandw < 1 ? 8 : bandw;
+    *plain_bands = remap && remap[0] == 'b';
+}
+
+void mxk_last_gemm_group(int* problems, int64_t* blocks) {
+    *problems = g_last_gemm_group_problems;
+    *blocks = g_last_gemm_group_blocks;
+}
+
+// One launch over the union of the tiles of plan's launched problems. The
+// device table goes into `ws` (plan.table_bytes() or more) on `stream`
+// ahead of the launch. ONE staging buffer suffices: every entry of the C
+// ABI synchronises with its GEMM stream before it returns, so no earlier
+// grouped launch can still be reading the table when the next call
+// overwrites it; for the same reason the host vectors of `plan` only have
+// to outlive the caller's synchronisation.
+int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
+                     const mx_group_plan* plan, void* ws, hipStream_t stream) {
+    const int count = (int)plan->entries.size();
+    if (count == 0) return 0;
+    const size_t eb = (size_t)count * sizeof(mx_group_entry);
+    if (hipMemcpyAsync(ws, plan->entries.data(), eb, hipMemcpyHostToDevice,
+                       stream) != hipSuccess ||
+        hipMemcpyAsync((char*)ws + eb, plan->tile_start.data(),
+                       (size_t)(count + 1) * sizeof(int32_t),
+                       hipMemcpyHostToDevice, stream) != hipSuccess)
+        return -2;
+    static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
+    const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
+                      : loopenv[0] == 'p' ? 1 : -1;
+    const unsigned blocks = (unsigned)plan->blocks();
+    const int band0 = plan->entries[0].band;
+    const mx_group_entry* table = (const mx_group_entry*)ws;
+    auto form = [&](auto t, auto beta) {
+        using T = decltype(t);
+        constexpr int BT = decltype(beta)::value;
+        auto l = [&](auto ta, auto tb) {
+            launch_gemm_grouped<T, BT, decltype(ta)::value,
+                                decltype(tb)::value>(
+                count, blocks, band0, table, loopsel, plan->pitch32, stream);
+        };
+        using one = std::integral_constant<int, 1>;
+        using zero = std::integral_constant<int, 0>;
+        if (trans_a && trans_b) l(one{}, one{});
+        else if (trans_a)       l(one{}, zero{});
+        else if (trans_b)       l(zero{}, one{});
+        else                    l(zero{}, zero{});
+    };
+    using one = std::integral_constant<int, 1>;
+    using zero = std::integral_constant<int, 0>;
+    if (is_fp32) { if (beta_one) form(float{}, one{}); else form(float{}, zero{}); }
+    else         { if (beta_one) form(double{}, one{}); else form(double{}, zero{}); }
+    return (int)hipGetLastError() == 0 ? 0 : -2;
+}
 
 void mxk_last_gemm_config(mx_gemm_cfg_t* out) { *out = g_last_gemm_cfg; }
 
@@ -835,7 +985,7 @@ int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K,
     hipLaunchKernelGGL(
         (gemm_mfma_kernel<float, 0, 16, 128, 2, 2, 0, 0, 0, EPI_TN_ADD>),
         grid, block, 0, stream, M, N, K, A, lda, B, ldb, C, ldc, nbm, band,
-        0, addC);
+        0, addC, (const mx_group_entry*)nullptr);
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 

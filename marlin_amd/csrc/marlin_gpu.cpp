@@ -26,6 +26,7 @@
 
 #include "../../include/marlin_gpu.h"
 #include "gemm_op_layout.h"
+#include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
 
 // kernels.hip launchers
 extern "C" {
@@ -55,6 +56,10 @@ int mxk_gemv(int is_fp32, int64_t m, int64_t n, int64_t lda, const void* A,
              const void* x, double* partial, void* y, hipStream_t stream);
 void mxk_last_gemm_config(mx_gemm_cfg_t* out);
 void mxk_last_gemm_loop(int* out);
+void mxk_gemm_remap_knobs(int* band_width, int* plain_bands);
+void mxk_last_gemm_group(int* problems, int64_t* blocks);
+int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
+                     const mx_group_plan* plan, void* ws, hipStream_t stream);
 }
 
 #define HIP_OK(x)                                                        \
@@ -93,11 +98,6 @@ int64_t mx_slab_off(int64_t total, int parts, int idx) {
   return (int64_t)idx * bl;
 }
 
-struct mx_dbuf {
-  void* ptr = nullptr;
-  int64_t bytes = 0;
-};
-
 struct mx_ctx {
   int device = 0;
   hipStream_t s_gemm = nullptr;
@@ -111,6 +111,9 @@ struct mx_ctx {
   bool have_comm = false;
   // cached workspaces for the host-buffer entries
   mx_dbuf wsA, wsB, wsC, wsPA[2], wsPB[2];
+  // grouped GEMM: the device table's staging buffer and its host image
+  mx_dbuf wsG;
+  mx_group_plan group_plan;
   mx_stats_t st = {};
 };
 
@@ -176,7 +179,8 @@ int mx_shutdown(mx_ctx* c) {
   if (c->colc && c->colc != c->world) ncclCommDestroy(c->colc);
   if (c->world) ncclCommDestroy(c->world);
   for (mx_dbuf* b : {&c->wsA, &c->wsB, &c->wsC,
-                     &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1]})
+                     &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1],
+                     &c->wsG})
     if (b->ptr) (void)hipFree(b->ptr);
   for (int i = 0; i < 16; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -445,6 +449,51 @@ int mx_gemm_device_op(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
   c->st.flops = 2.0 * m * k * n;
   return gemm_device(c, is_fp32, beta_one, m, k, n, dA->ptr, lda, dB->ptr,
                      ldb, dC->ptr, ldc, trans_a, trans_b);
+}
+
+// Many independent products in one launch (include/marlin_gpu.h). The
+// plan (gemm_group_plan.h) validates the whole table first; only then is
+// anything enqueued.
+int mx_gemm_device_grouped(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
+                           int trans_b, int count,
+                           const mx_gemm_problem_t* problems) {
+  if (!c) return MX_EINVAL;
+  int band_width = 8, plain_bands = 0;
+  mxk_gemm_remap_knobs(&band_width, &plain_bands);
+  mx_group_plan& plan = c->group_plan;
+  int rc = mx_gemm_group_plan(is_fp32, beta_one, trans_a, trans_b, band_width,
+                              plain_bands, count, problems, &plan);
+  c->st = {};
+  if (rc) return rc;
+  c->st.flops = plan.flops;
+  if (plan.entries.empty() && plan.zeros.empty()) return MX_OK;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t es = is_fp32 ? 4 : 8;
+  for (const mx_group_zero& z : plan.zeros)
+    HIP_OK(hipMemset2DAsync(z.C, (size_t)z.ldc * es, 0, (size_t)z.m * es,
+                            (size_t)z.n, c->s_gemm));
+  if (plan.entries.empty()) {
+    HIP_OK(hipStreamSynchronize(c->s_gemm));
+    return MX_OK;
+  }
+  if ((rc = ensure(c, &c->wsG, plan.table_bytes()))) return rc;
+  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
+  rc = mxk_gemm_grouped(is_fp32, beta_one, trans_a, trans_b, &plan,
+                        c->wsG.ptr, c->s_gemm);
+  if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
+  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
+  HIP_OK(hipEventSynchronize(c->ev[1]));
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->st.gemm_ms += ms;
+  c->st.gemm_launches += 1;
+  return MX_OK;
+}
+
+int mx_last_gemm_group(mx_ctx* c, int* problems_launched, int64_t* blocks) {
+  if (!c || !problems_launched || !blocks) return MX_EINVAL;
+  mxk_last_gemm_group(problems_launched, blocks);
+  return MX_OK;
 }
 
 int mx_last_gemm_op(mx_ctx* c, int* trans_a, int* trans_b) {

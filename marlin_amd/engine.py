@@ -43,6 +43,19 @@ class MxGemmCfg(ctypes.Structure):
         "is_fp32", "beta_one", "bk", "bm", "waves", "band", "phase_mask")]
 
 
+class MxGemmProblem(ctypes.Structure):
+    """mx_gemm_problem_t: one product of a grouped GEMM call."""
+    _fields_ = [
+        ("m", ctypes.c_int64), ("k", ctypes.c_int64), ("n", ctypes.c_int64),
+        ("dA", ctypes.c_void_p), ("a_off", ctypes.c_int64),
+        ("lda", ctypes.c_int64),
+        ("dB", ctypes.c_void_p), ("b_off", ctypes.c_int64),
+        ("ldb", ctypes.c_int64),
+        ("dC", ctypes.c_void_p), ("c_off", ctypes.c_int64),
+        ("ldc", ctypes.c_int64),
+    ]
+
+
 def _load():
     if not os.path.exists(_SO):
         raise EngineUnavailable(
@@ -139,6 +152,9 @@ def _load():
                                       vp]),
         "mx_last_gemm_op": (ctypes.c_int, [vp, P(ctypes.c_int),
                                            P(ctypes.c_int)]),
+        "mx_gemm_device_grouped": (ctypes.c_int, [vp] + [ctypes.c_int] * 5
+                                   + [P(MxGemmProblem)]),
+        "mx_last_gemm_group": (ctypes.c_int, [vp, P(ctypes.c_int), P(i64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -652,6 +668,74 @@ class Engine:
                                     B.buf, B.pitch, C.buf, C.pitch),
             "mx_gemm_device_op")
         return C
+
+    def gemm_grouped_raw(self, problems, fp32=False, accumulate=False,
+                         trans_a=False, trans_b=False, check=True):
+        """mx_gemm_device_grouped on explicit tuples
+        (m, k, n, bufA, offA, lda, bufB, offB, ldb, bufC, offC, ldc):
+        padded dims, device buffers from alloc(), offsets and pitches in
+        elements. One launch over the tiles of all the problems. Returns
+        the entry's code; check=True raises on a non-zero one. problems
+        may be None (a NULL table)."""
+        count, table = 0, None
+        if problems is not None:
+            count = len(problems)
+            table = (MxGemmProblem * max(count, 1))()
+            for t, q in zip(table, problems):
+                (t.m, t.k, t.n, t.dA, t.a_off, t.lda, t.dB, t.b_off, t.ldb,
+                 t.dC, t.c_off, t.ldc) = [
+                    v.value if isinstance(v, ctypes.c_void_p) else v
+                    for v in q]
+        return self._grouped_call(count, table, fp32, accumulate, trans_a,
+                                  trans_b, check)
+
+    def _grouped_call(self, count, table, fp32, accumulate, trans_a, trans_b,
+                      check=True):
+        rc = lib().mx_gemm_device_grouped(
+            self._ctx, 1 if fp32 else 0, 1 if accumulate else 0,
+            int(trans_a), int(trans_b), count, table)
+        if check:
+            _ck(rc, "mx_gemm_device_grouped")
+        return rc
+
+    def gemm_grouped(self, problems, accumulate=False, trans_a=False,
+                     trans_b=False):
+        """Many independent device-resident products C_i (+)= op(A_i) @
+        op(B_i) in ONE kernel launch. problems is a list of (A, B, C)
+        DeviceMatrix triples; C=None allocates as gemm_dd does (not with
+        accumulate). Type, accumulate and the op form are uniform per
+        call, shapes are per problem. Padded-dim rule and pitch asserts
+        are gemm_dd's, and every result is bit-identical to gemm_dd on
+        that triple alone. Returns the list of C handles."""
+        out, rows = [], []
+        fp32 = problems[0][0].fp32 if problems else False
+        for A, B, C in problems:
+            assert A.fp32 == B.fp32 == fp32
+            m, k, n = gemm_op_shape((A.m, A.n), (B.m, B.n), trans_a, trans_b)
+            mp = (m + 127) // 128 * 128
+            kp = (k + 15) // 16 * 16
+            np_ = (n + 127) // 128 * 128
+            if C is None:
+                assert not accumulate
+                C = DeviceMatrix(self, self.alloc(mp * np_ * A.elem), m, n,
+                                 mp, A.fp32)
+            assert C.pitch == mp and C.m == m and C.n == n
+            assert A.pitch >= (kp if trans_a else mp)
+            assert B.pitch >= (np_ if trans_b else kp)
+            out.append(C)
+            rows.append((mp, kp, np_, A.buf, 0, A.pitch, B.buf, 0, B.pitch,
+                         C.buf, 0, C.pitch))
+        self.gemm_grouped_raw(rows, fp32, accumulate, trans_a, trans_b)
+        return out
+
+    def last_gemm_group(self):
+        """(problems that reached the kernel, grid blocks) of the last
+        grouped launch; (0, 0) before the first."""
+        npb, blocks = ctypes.c_int(-1), ctypes.c_int64(-1)
+        _ck(lib().mx_last_gemm_group(self._ctx, ctypes.byref(npb),
+                                     ctypes.byref(blocks)),
+            "mx_last_gemm_group")
+        return npb.value, blocks.value
 
     # -- device-resident bench path ------------------------------------------
     def alloc(self, nbytes):

@@ -38,7 +38,18 @@ def _upload_blocks(eng, a, nb, offs, lens):
             for i in range(nb) for j in range(nb)}
 
 
-def lu_decompose(dvm, mode="auto", base_size=1000):
+def _gemm_batch(eng, problems, grouped, **kw):
+    """A batch of mutually independent device GEMMs, (A, B, C) triples as
+    Engine.gemm_grouped takes them: one grouped launch, or (grouped=False,
+    the comparison arm) one launch and host sync per product. Both give
+    the same bits. A batch of one has nothing to share a launch with and
+    takes the plain entry either way. Returns the C handles."""
+    if grouped and len(problems) > 1:
+        return eng.gemm_grouped(problems, **kw)
+    return [eng.gemm_dd(A, B, C, **kw) for A, B, C in problems]
+
+
+def lu_decompose(dvm, mode="auto", base_size=1000, grouped=True):
     """DenseVecMatrix.luDecompose (DenseVecMatrix.scala:283-464).
     Returns (BlockMatrix with packed L\\U, p_array) where p_array[g] is
     the source row of output row g within its block row."""
@@ -83,22 +94,25 @@ def lu_decompose(dvm, mode="auto", base_size=1000):
         d_Minv = eng.upload_matrix(np.linalg.solve(L, P))     # L^-1 P
         d_negMinv = eng.upload_matrix(-np.linalg.solve(L, P))
         d_Uinv = eng.upload_matrix(np.linalg.inv(U))          # U^-1
-        # panel scales + trailing update — device-resident GEMMs
-        negA2 = {}
-        for j in range(i + 1, nb):
-            negA2[j] = eng.gemm_dd(d_negMinv, blk[(i, j)])    # -L^-1 P A12
-            new = eng.gemm_dd(d_Minv, blk[(i, j)])            # U12 panel
+        # panel scales + trailing update — device-resident GEMMs; the
+        # scales of a step are one batch, its trailing update the next
+        rest = range(i + 1, nb)
+        scales = ([(d_negMinv, blk[(i, j)], None) for j in rest]  # -L^-1 P A12
+                  + [(d_Minv, blk[(i, j)], None) for j in rest]   # U12 panel
+                  + [(blk[(r, i)], d_Uinv, None) for r in rest])  # L21 panel
+        done = _gemm_batch(eng, scales, grouped)
+        nr = len(rest)
+        negA2 = dict(zip(rest, done[:nr]))
+        for j, new in zip(rest, done[nr:2 * nr]):
             blk[(i, j)].free()
             blk[(i, j)] = new
-        for r in range(i + 1, nb):
-            new = eng.gemm_dd(blk[(r, i)], d_Uinv)            # L21 panel
+        for r, new in zip(rest, done[2 * nr:]):
             blk[(r, i)].free()
             blk[(r, i)] = new
-        for r in range(i + 1, nb):
-            for j in range(i + 1, nb):
-                # A22 += L21 · (-U12)  (reference: A4 - A3 (A11 \\ A2))
-                eng.gemm_dd(blk[(r, i)], negA2[j], blk[(r, j)],
-                            accumulate=True)
+        # A22 += L21 · (-U12)  (reference: A4 - A3 (A11 \\ A2))
+        _gemm_batch(eng, [(blk[(r, i)], negA2[j], blk[(r, j)])
+                          for r in rest for j in rest], grouped,
+                    accumulate=True)
         for d in negA2.values():
             d.free()
         d_Minv.free(); d_negMinv.free(); d_Uinv.free()
@@ -119,7 +133,7 @@ def lu_decompose(dvm, mode="auto", base_size=1000):
     return (BlockMatrix(host, n, n, engine=dvm._eng), p_array)
 
 
-def inverse(dvm, mode="auto", base_size=1000):
+def inverse(dvm, mode="auto", base_size=1000, grouped=True):
     """DenseVecMatrix.inverse (DenseVecMatrix.scala:565-764)."""
     from .api import BlockMatrix
 
@@ -146,39 +160,38 @@ def inverse(dvm, mode="auto", base_size=1000):
         S1[i] = inv
         d_inv = eng.upload_matrix(inv)
         d_neg = eng.upload_matrix(-inv)
-        for j in range(i + 1, nb):
-            S2[(i, j)] = eng.gemm_dd(d_neg, blk[(i, j)])      # -A11^-1 A12
-        for r in range(i + 1, nb):
-            S3[(r, i)] = eng.gemm_dd(blk[(r, i)], d_neg)      # -A21 A11^-1
-        for r in range(i + 1, nb):
-            for j in range(i + 1, nb):
-                # A22 += A21 · (-A11^-1 A12)
-                eng.gemm_dd(blk[(r, i)], S2[(i, j)], blk[(r, j)],
-                            accumulate=True)
+        rest = range(i + 1, nb)
+        done = _gemm_batch(
+            eng, [(d_neg, blk[(i, j)], None) for j in rest]     # -A11^-1 A12
+            + [(blk[(r, i)], d_neg, None) for r in rest],       # -A21 A11^-1
+            grouped)
+        for j, d in zip(rest, done[:len(rest)]):
+            S2[(i, j)] = d
+        for r, d in zip(rest, done[len(rest):]):
+            S3[(r, i)] = d
+        # A22 += A21 · (-A11^-1 A12)
+        _gemm_batch(eng, [(blk[(r, i)], S2[(i, j)], blk[(r, j)])
+                          for r in rest for j in rest], grouped,
+                    accumulate=True)
         d_inv.free(); d_neg.free()
     last = eng.download_matrix(blk[(nb - 1, nb - 1)])
     T = {(nb - 1, nb - 1): eng.upload_matrix(np.linalg.inv(last))}
 
     # backward sweep (DenseVecMatrix.scala:677-764) — device-resident
     for i in range(nb - 2, -1, -1):
-        col = {}
-        for r in range(i + 1, nb):
-            acc = None
-            for c in range(i + 1, nb):
-                if acc is None:
-                    acc = eng.gemm_dd(T[(r, c)], S3[(c, i)])
-                else:
-                    eng.gemm_dd(T[(r, c)], S3[(c, i)], acc, accumulate=True)
-            col[r] = acc                                      # inv[r, i]
-        row = {}
-        for c in range(i + 1, nb):
-            acc = None
-            for j in range(i + 1, nb):
-                if acc is None:
-                    acc = eng.gemm_dd(S2[(i, j)], T[(j, c)])
-                else:
-                    eng.gemm_dd(S2[(i, j)], T[(j, c)], acc, accumulate=True)
-            row[c] = acc                                      # inv[i, c]
+        # col[r] = sum_c T[r, c] S3[c, i] (inv[r, i]) and row[c] =
+        # sum_j S2[i, j] T[j, c] (inv[i, c]): the chains are independent
+        # of one another, so position t of every chain is one batch
+        rest = range(i + 1, nb)
+        col = dict.fromkeys(rest)
+        row = dict.fromkeys(rest)
+        for t in rest:
+            done = _gemm_batch(
+                eng, [(T[(r, t)], S3[(t, i)], col[r]) for r in rest]
+                + [(S2[(i, t)], T[(t, c)], row[c]) for c in rest],
+                grouped, accumulate=t > i + 1)
+            col = dict(zip(rest, done[:len(rest)]))
+            row = dict(zip(rest, done[len(rest):]))
         corner = eng.upload_matrix(S1[i])
         for j in range(i + 1, nb):
             eng.gemm_dd(S2[(i, j)], col[j], corner, accumulate=True)
@@ -196,7 +209,7 @@ def inverse(dvm, mode="auto", base_size=1000):
     return BlockMatrix(out, n, n, engine=dvm._eng)
 
 
-def cholesky_decompose(dvm, mode="auto", base_size=1000):
+def cholesky_decompose(dvm, mode="auto", base_size=1000, grouped=True):
     """DenseVecMatrix.choleskyDecompose (DenseVecMatrix.scala:475-566):
     A = L L^T, lower-triangular L. Right-looking blocked: host chol of
     the (symmetrized, as the reference does) diagonal block, panel scale
@@ -231,18 +244,19 @@ def cholesky_decompose(dvm, mode="auto", base_size=1000):
         linvT = np.linalg.inv(L11).T                 # L11^-T (host, base)
         d_pos = eng.upload_matrix(linvT)
         d_neg = eng.upload_matrix(-linvT)
-        neg = {}
-        for r in range(i + 1, nb):
-            old = blk[(r, i)]
-            l21 = eng.gemm_dd(old, d_pos)            # L21 panel
-            neg[r] = eng.gemm_dd(old, d_neg)         # -L21
-            old.free()
+        rest = range(i + 1, nb)
+        done = _gemm_batch(
+            eng, [(blk[(r, i)], d_pos, None) for r in rest]     # L21 panel
+            + [(blk[(r, i)], d_neg, None) for r in rest],       # -L21
+            grouped)
+        neg = dict(zip(rest, done[len(rest):]))
+        for r, l21 in zip(rest, done[:len(rest)]):
+            blk[(r, i)].free()
             blk[(r, i)] = l21
-        for c in range(i + 1, nb):
-            for r in range(c, nb):
-                # A22 += L21[r] @ (-L21[c])^T, -L21[c] read as stored
-                eng.gemm_dd(blk[(r, i)], neg[c], blk[(r, c)],
-                            accumulate=True, trans_b=True)
+        # A22 += L21[r] @ (-L21[c])^T, -L21[c] read as stored
+        _gemm_batch(eng, [(blk[(r, i)], neg[c], blk[(r, c)])
+                          for c in rest for r in range(c, nb)], grouped,
+                    accumulate=True, trans_b=True)
         for d in neg.values():
             d.free()
         d_pos.free()

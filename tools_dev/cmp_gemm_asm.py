@@ -15,14 +15,15 @@ CLASSES = (("mfma", r"v_mfma_"), ("lds_rd", r"ds_read"),
 
 
 def key_of(demangled):
-    # gemm_mfma_kernel<T, BETA, BK, BM, WM, WN, PIPE, TA, TB[, EPI]>
+    # gemm_mfma_kernel<T, BETA, BK, BM, WM, WN, PIPE, TA, TB[, EPI[, GRP]]>
     m = re.match(r"void gemm_mfma_kernel<([^>]*)>", demangled)
     if m:
         a = [x.strip() for x in m.group(1).split(",")]
-        a += ["0"] * (10 - len(a))
+        a = [re.sub(r"^\(\w+\)", "", x) for x in a]     # (EPI)1 -> 1
+        a += ["0"] * (11 - len(a))
         return tuple(a)
     if demangled.startswith("sgemm_mfma_tn_epilogue_kernel"):
-        return ("float", "0", "16", "128", "2", "2", "0", "0", "0", "1")
+        return ("float", "0", "16", "128", "2", "2", "0", "0", "0", "1", "0")
     return None
 
 
@@ -94,8 +95,11 @@ def loop_counts(ins):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    assert set(old) == set(new), set(old) ^ set(new)
-    print("| kernel <T,BETA,BK,BM,WM,WN,PIPE,TA,TB,EPI> | instr old/new | "
+    # a kernel only the new listing has (a new instantiation family) is
+    # shown against its twin with the trailing GRP argument cleared
+    assert set(old) <= set(new), set(old) - set(new)
+    added = sorted(set(new) - set(old))
+    print("| kernel <T,BETA,BK,BM,WM,WN,PIPE,TA,TB,EPI,GRP> | instr old/new | "
           "identical | VGPR | SGPR | scratch | LDS | occ | loop "
           + "/".join(n for n, _ in CLASSES) + " |")
     print("|---|---|---|---|---|---|---|---|---|")
@@ -118,8 +122,20 @@ def main():
         print(f"| {','.join(k)} | {o['n']}/{n['n']} | "
               f"{'yes' if same else 'no'} | {pair('vgpr')} | {pair('sgpr')} | "
               f"{pair('scratch')} | {pair('lds')} | {pair('occ')} | {loop} |")
+    for k in added:
+        n, t = new[k], new.get(k[:-1] + ("0",))
+        loop = "/".join(map(str, n["loop"]))
+        twin = "no twin"
+        if t:
+            twin = ("twin loop equal" if t["loop"] == n["loop"] else
+                    "twin loop " + "/".join(map(str, t["loop"])))
+            twin += f", twin instr {t['n']} VGPR {t['vgpr']} SGPR {t['sgpr']}"
+        print(f"| {','.join(k)} | new/{n['n']} | new | {n['vgpr']} | "
+              f"{n['sgpr']} | {n['scratch']} | {n['lds']} | {n['occ']} | "
+              f"{loop} ({twin}) |")
     ident = sum(old[k]["ins"] == new[k]["ins"] for k in old)
-    print(f"\n{len(old)} kernels, {ident} identical, {bad} failing a "
+    print(f"\n{len(old)} kernels, {ident} identical, {len(added)} new, "
+          f"{bad} failing a "
           "condition (scratch up, occupancy down, loop MFMA/DMA/barrier "
           "counts changed)")
     return 1 if bad else 0
