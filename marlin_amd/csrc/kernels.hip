@@ -150,7 +150,12 @@ DEVFN void block_remap(int id, int nbn, int nbm, int band, int& bm, int& bn) {
 // 67.9 TF at 20000^3 with the two-barrier loop. With the pipelined loop
 // the default reaches 70.4 and bk32 62.6 at 20000^3, and at 20480^3 (the
 // nearest size a 256-row tile divides) the default 71.4 vs bm256 70.2:
-// the ranking holds (profiles/r03_pipelined_loop.md).
+// the ranking holds (profiles/r03_pipelined_loop.md). With the fragment
+// reads pinned and the steady state unrolled for a constant buffer the
+// default reaches 73.6 and bk32 69.6 at 20000^3; at 20480^3 bm256 (75.6)
+// is then 0.85% ahead of the default (75.0), which stays the default:
+// 20000 pads to 20096 rows, which 256 does not divide
+// (profiles/r05_loop_waits.md).
 //
 // PIPE selects the k-loop (both accumulate in the same order, so their
 // results are bit-identical):
@@ -347,7 +352,8 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     } else {
     // Pipelined loop: every wave hides its own loop-top work. Step s
     // (tile s in buffer s & 1) runs
-    //     quads 0 .. Q-2:  read quad q+1's fragments, MFMAs of quad q
+    //     quads 0 .. Q-2:  MFMAs of quad q, with quad q+1's fragment reads
+    //                      pinned behind the first of them (below)
     //     lgkmcnt(0)       quad Q-1's fragments are in registers: this
     //                      wave has finished reading tile s
     //     vmcnt(0)         this wave's pieces of tile s+1 (issued a full
@@ -361,6 +367,17 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // tile left to issue / to read), which keeps the steady-state body
     // one branch-free block the scheduler hints can order.
     //
+    // Every quad is a scheduling region of its own (sched_barrier(0)), and
+    // inside it the reads of the next quad sit behind the first MFMAs.
+    // Left free, the machine scheduler packed the reads of two quads into
+    // one and issued the last of them 0..1 MFMAs ahead of an lgkmcnt(0):
+    // twice per step, once right in front of the barrier, every wave sat
+    // out an LDS round trip with no MFMA of its own queued. Now no wait of
+    // the steady state forces a read younger than RD_TAIL MFMAs
+    // (tools_dev/gemm_loop_waits.py prints the distances from the compiled
+    // code, tests/test_gemm_loop_waits.py holds them;
+    // profiles/r05_loop_waits.md).
+    //
     // DMA sources: (wave-uniform running pointer + uniform per-piece
     // offset) + per-lane 32-bit byte offset. The lane offsets hold the
     // XOR swizzle and are loop-invariant; the pointers advance by one
@@ -368,6 +385,36 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     // wraps. The launcher guarantees the lane offsets fit 32 bits.
     constexpr int Q = BK / 4;
     static_assert(Q % 2 == 0, "fragment registers ping-pong per quad");
+    // Placement of a quad's MT + NT fragment reads among the previous
+    // quad's MT * NT MFMAs: RD_PER reads behind each of the first
+    // RD_GROUPS MFMAs, so that at least RD_TAIL MFMAs (4 x 64 cycles, more
+    // than an LDS round trip) lie between the last read and the wait in
+    // front of the fragments' first use.
+    constexpr int RD_TAIL = 4;
+    static_assert(MT * NT > RD_TAIL, "a quad needs MFMAs ahead of its tail");
+    constexpr int RD_PER = (MT + NT + MT * NT - RD_TAIL - 1) / (MT * NT - RD_TAIL);
+    constexpr int RD_GROUPS = (MT + NT + RD_PER - 1) / RD_PER;
+    // fp32 starts the reads RD_LEAD MFMAs into the quad: with the reads
+    // right behind the first MFMA the BETA=1 A*B^T form needs 129 VGPRs
+    // and drops from 4 to 3 waves per SIMD.
+    constexpr int RD_LEAD =
+        sizeof(T) == 4 ? (MT * NT - RD_GROUPS - RD_TAIL) / 2 : 0;
+    // The last quad of a step puts the next tile's quad-0 reads behind its
+    // first MFMAs and the DMA pieces behind the following ones. The 8-wave
+    // geometries take two reads per MFMA there: bk32 has 8 MFMAs for 6
+    // reads, and bm256's reads pair up less once the buffer is a constant,
+    // which would take the loop-top wait from 11 MFMAs of distance to 9.
+    constexpr int LQ_PER = NWAVES == 8 ? 2 : 1;
+    constexpr int LQ_GROUPS = (MT + NT + LQ_PER - 1) / LQ_PER;
+    // Steady state unrolled by two steps: the buffer is a constant in each
+    // half, so the fragment addresses are loop-invariant VGPR bases with
+    // immediate offsets and the DMA m0 values are SGPR constants (34 -> 8
+    // non-MFMA VALU and 48 -> 39 SALU instructions per step in the fp64
+    // default). One step at run-time parity follows when the steady-state
+    // count is odd. Not for fp32 BETA=1 at BK=16: those forms sit at the
+    // 128-VGPR limit of 4 waves per SIMD and the hoisted bases cost A^T*B
+    // a wave (138 VGPRs).
+    constexpr bool UNROLL2 = !(sizeof(T) == 4 && BETA && BK == 16);
     const int swid = __builtin_amdgcn_readfirstlane(wid);
     // These two loops stay in the kernel body: behind a function, struct
     // or lambda the same arithmetic gave the steady-state loop another
@@ -421,18 +468,31 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
     __builtin_amdgcn_s_barrier();            // tile 0 visible
     read_quad(As, Bs, 0, fa[0], fb[0]);
 
-    // AHEAD: tiles that follow tile s; 2 or more = steady state
-    auto step = [&](int s, auto ahead) {
+    // AHEAD: tiles that follow this step's tile; 2 or more = steady
+    // state. bufc: the tile's buffer, an int or an integral_constant.
+    auto step = [&](auto bufc, auto ahead) {
         constexpr int AHEAD = decltype(ahead)::value;
-        const int buf = s & 1;
+        const int buf = bufc;
         const T* At = &As[buf * BK * BM];
         const T* Bt = &Bs[buf * BN * BK];
         #pragma unroll
         for (int q = 0; q + 1 < Q; q++) {
             read_quad(At, Bt, q + 1, fa[(q + 1) & 1], fb[(q + 1) & 1]);
             mfma_quad(fa[q & 1], fb[q & 1]);
+            // quad q+1's reads stay in quad q's region, RD_PER behind
+            // each of its first MFMAs, and RD_TAIL or more MFMAs follow
+            // the last read before the region ends
+            if constexpr (RD_LEAD > 0)
+                __builtin_amdgcn_sched_group_barrier(0x008, RD_LEAD, 0);
+            #pragma unroll
+            for (int g = 0; g < RD_GROUPS; g++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, RD_PER, 0);  // DS read
+            }
+            __builtin_amdgcn_sched_group_barrier(
+                0x008, MT * NT - RD_LEAD - RD_GROUPS, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if constexpr (AHEAD >= 1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -446,11 +506,11 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         }
         mfma_quad(fa[1], fb[1]);             // quad Q-1 of tile s
         if constexpr (AHEAD >= 1) {
-            // one fragment read, then one DMA piece, behind each MFMA
+            // LQ_PER fragment reads, then one DMA piece, behind each MFMA
             #pragma unroll
-            for (int g = 0; g < MT + NT; g++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+            for (int g = 0; g < LQ_GROUPS; g++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, LQ_PER, 0);  // DS read
             }
             if constexpr (AHEAD >= 2) {
                 #pragma unroll
@@ -462,10 +522,17 @@ __global__ void gemm_mfma_kernel(int64_t M, int64_t N, int64_t K,
         }
         __builtin_amdgcn_sched_barrier(0);
     };
+    using std::integral_constant;
     int s = 0;
-    for (; s + 2 < ntiles; s++) step(s, std::integral_constant<int, 2>{});
-    if (s + 1 < ntiles) { step(s, std::integral_constant<int, 1>{}); s++; }
-    step(s, std::integral_constant<int, 0>{});
+    if constexpr (UNROLL2) {
+        for (; s + 3 < ntiles; s += 2) {
+            step(integral_constant<int, 0>{}, integral_constant<int, 2>{});
+            step(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+        }
+    }
+    for (; s + 2 < ntiles; s++) step(s & 1, integral_constant<int, 2>{});
+    if (s + 1 < ntiles) { step(s & 1, integral_constant<int, 1>{}); s++; }
+    step(s & 1, integral_constant<int, 0>{});
     }
 
     if constexpr (EPI == EPI_TN_ADD) {
