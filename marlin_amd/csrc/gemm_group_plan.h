@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/marlin_gpu.h"
+#include "gemm_launch_policy.h"   // the pitch bound of the pipelined loop
 
 // The device buffer behind the opaque handle of the C ABI; bytes is what
 // lets the plan refuse a region that does not fit.
@@ -67,7 +68,7 @@ struct mx_group_plan {
   std::vector<mx_group_zero> zeros;
   std::vector<int> order;              // entries[i] is problems[order[i]]
   double flops = 0;                    // sum of 2mkn over the whole table
-  bool pitch32 = true;                 // every A/B pitch below 2^26 elements
+  bool pitch32 = true;                 // every A/B pitch: mx_gemm_pitch32
   int64_t blocks() const { return tile_start.empty() ? 0 : tile_start.back(); }
   int64_t table_bytes() const {
     return (int64_t)(entries.size() * sizeof(mx_group_entry) +
@@ -188,8 +189,7 @@ static inline int mx_gemm_group_plan(int is_fp32, int beta_one, int trans_a,
     e.nbn = (int32_t)(q.n / 128);
     e.band = e.nbn < band_width ? e.nbn : band_width;
     if (plain_bands) e.band = -e.band;
-    if (q.lda >= ((int64_t)1 << 26) || q.ldb >= ((int64_t)1 << 26))
-      out->pitch32 = false;
+    if (!mx_gemm_pitch32(q.lda, q.ldb)) out->pitch32 = false;
     out->entries.push_back(e);
     out->tile_start.push_back((int32_t)start);
     start += (int64_t)e.nbm * e.nbn;

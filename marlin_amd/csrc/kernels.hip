@@ -41,8 +41,9 @@
 
 #include <type_traits>
 
-#include "../../include/marlin_gpu.h"   // mx_gemm_cfg_t
-#include "gemm_group_plan.h"            // mx_group_entry (the device table)
+#include "kernels.h"                // the launchers' prototypes
+#include "gemm_group_plan.h"        // mx_group_entry (the device table)
+#include "gemm_launch_policy.h"     // which instantiation a launch runs
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -779,102 +780,76 @@ __global__ void gemv_reduce_kernel(int64_t m, int nchunks,
 }
 
 // ---------------------------------------------------------------------------
-// What mxk_gemm last launched (mx_last_gemm_config): the env knobs of
-// mxk_gemm_op are latched per process, so a test can only prove which
-// instantiation it exercised by reading this record back.
-static mx_gemm_cfg_t g_last_gemm_cfg = {};
-// k-loop of that launch (mx_last_gemm_loop): 0 = two-barrier, 1 = pipelined
-static int g_last_gemm_loop = 0;
-// op(A), op(B) of that launch (mx_last_gemm_op): 1 = transposed
-static int g_last_gemm_op[2] = {0, 0};
+// GEMM launch. Which instantiation a call runs is decided in
+// gemm_launch_policy.h; here are the latched knobs, the record of the last
+// launch, the one step from a selected variant to its compiled kernel, and
+// the launchers, which differ in their checks, grid size and arguments.
 
-// The runtime half of a GEMM launch; the template arguments of launch_gemm
-// are the compile-time half.
-struct gemm_call {
+// The MARLIN_GEMM_* knobs, read once per process.
+static const mx_gemm_knobs& gemm_knobs() {
+    static const mx_gemm_knobs k = mx_gemm_parse_knobs(getenv);
+    return k;
+}
+
+// What mxk_gemm_op / mxk_gemm_grouped last launched (kernels.h).
+static mxk_last_gemm_t g_last_gemm = {};
+
+static void record_launch(const mx_gemm_variant& v) {
+    g_last_gemm.cfg = mx_gemm_cfg_t{v.T, v.BETA, v.BK, v.BM, v.WM * v.WN,
+                                    v.band, v.phase_mask};
+    g_last_gemm.loop = v.PIPE;
+    g_last_gemm.trans_a = v.TA;
+    g_last_gemm.trans_b = v.TB;
+}
+
+// The kernel arguments of one launch, not yet typed.
+struct gemm_args {
     int64_t M, N, K;
     const void* A; int64_t lda;
     const void* B; int64_t ldb;
     void* C; int64_t ldc;
-    int band, phase_mask;
-    int loopsel;            // MARLIN_GEMM_LOOP: 0 twobar, 1 pipe, -1 unset
-    bool pitch32;           // the pipelined loop's 32-bit lane offsets fit
-    hipStream_t stream;
+    int nbm, band, phase_mask;
+    const void* addC;
+    const mx_group_entry* grp;
 };
 
-// Picks the k-loop, launches that instantiation, records what it launched.
-template <typename T, int BETA, int BK, int BM, int WM, int WN,
-          int TA = 0, int TB = 0>
-static void launch_gemm(const gemm_call& g) {
-    const bool pipe = g.pitch32 && (g.loopsel >= 0 ? g.loopsel == 1
-                                    : !(sizeof(T) == 4 && BK == 16));
-    g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(T) == 4, BETA, BK, BM, WM * WN,
-                                    g.band, g.phase_mask};
-    g_last_gemm_loop = pipe ? 1 : 0;
-    g_last_gemm_op[0] = TA;
-    g_last_gemm_op[1] = TB;
-    auto go = [&](auto pipe_c) {
-        hipLaunchKernelGGL(
-            (gemm_mfma_kernel<T, BETA, BK, BM, WM, WN, decltype(pipe_c)::value,
-                              TA, TB>),
-            dim3((unsigned)((g.M / BM) * (g.N / 128))), dim3(WM * WN * 64),
-            0, g.stream, g.M, g.N, g.K, (const T*)g.A, g.lda,
-            (const T*)g.B, g.ldb, (T*)g.C, g.ldc, (int)(g.M / BM), g.band,
-            g.phase_mask, (const T*)nullptr,
-            (const mx_group_entry*)nullptr);
-    };
-    if (pipe) go(std::integral_constant<int, 1>{});
-    else      go(std::integral_constant<int, 0>{});
+// Calls f(T{}, kernel) with the instantiation v names. It walks the closed
+// list of gemm_launch_policy.h, so exactly that list is compiled; a variant
+// outside it is a refused argument (-4), not a new kernel.
+template <class F>
+static int gemm_dispatch(const mx_gemm_variant& v, F&& f) {
+    int rc = -4;
+    mx_gemm_for_each_instantiation([&](auto inst) {
+        using I = decltype(inst);
+        if (!mx_gemm_same_kernel(I::variant(), v)) return;
+        using T = std::conditional_t<I::T != 0, float, double>;
+        f(T{}, gemm_mfma_kernel<T, I::BETA, I::BK, I::BM, I::WM, I::WN,
+                                I::PIPE, I::TA, I::TB, I::EPI, I::GRP>);
+        rc = 0;
+    });
+    return rc;
 }
 
-// problems and blocks of the last grouped launch (mx_last_gemm_group)
-static int g_last_gemm_group_problems = 0;
-static int64_t g_last_gemm_group_blocks = 0;
-
-// The grouped launch of one (type, beta, form): the default geometry, the
-// k-loop chosen as launch_gemm chooses it, phase 0.
-template <typename T, int BETA, int TA, int TB>
-static void launch_gemm_grouped(int count, unsigned blocks, int band0,
-                                const mx_group_entry* table, int loopsel,
-                                bool pitch32, hipStream_t stream) {
-    const bool pipe = pitch32 && (loopsel >= 0 ? loopsel == 1
-                                  : sizeof(T) != 4);
-    g_last_gemm_cfg = mx_gemm_cfg_t{sizeof(T) == 4, BETA, 16, 128, 4, band0, 0};
-    g_last_gemm_loop = pipe ? 1 : 0;
-    g_last_gemm_op[0] = TA;
-    g_last_gemm_op[1] = TB;
-    g_last_gemm_group_problems = count;
-    g_last_gemm_group_blocks = blocks;
-    auto go = [&](auto pipe_c) {
-        hipLaunchKernelGGL(
-            (gemm_mfma_kernel<T, BETA, 16, 128, 2, 2, decltype(pipe_c)::value,
-                              TA, TB, EPI_STORE, 1>),
-            dim3(blocks), dim3(256), 0, stream, (int64_t)0, (int64_t)0,
-            (int64_t)0, (const T*)nullptr, (int64_t)0, (const T*)nullptr,
-            (int64_t)0, (T*)nullptr, (int64_t)0, count, 0, 0,
-            (const T*)nullptr, table);
-    };
-    if (pipe) go(std::integral_constant<int, 1>{});
-    else      go(std::integral_constant<int, 0>{});
+static int gemm_launch(const mx_gemm_variant& v, unsigned blocks,
+                       const gemm_args& g, hipStream_t stream) {
+    const int rc = gemm_dispatch(v, [&](auto t, auto kernel) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(v.WM * v.WN * 64), 0,
+                           stream, g.M, g.N, g.K, (const T*)g.A, g.lda,
+                           (const T*)g.B, g.ldb, (T*)g.C, g.ldc, g.nbm, g.band,
+                           g.phase_mask, (const T*)g.addC, g.grp);
+    });
+    if (rc) return rc;
+    return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 
 // ---------------------------------------------------------------------------
-// C-visible launchers (called from marlin_gpu.cpp).
+// C-visible launchers (called from marlin_gpu.cpp; prototypes in kernels.h).
 extern "C" {
 
-// The latched remap knobs the grouped plan needs: MARLIN_GEMM_BAND width
-// (>= 1) and whether MARLIN_GEMM_REMAP=bands asks for plain bands.
-void mxk_gemm_remap_knobs(int* band_width, int* plain_bands) {
-    static const char* bandenv = getenv("MARLIN_GEMM_BAND");
-    static const char* remap = getenv("MARLIN_GEMM_REMAP");
-    int bandw = bandenv ? atoi(bandenv) : 8;
-    *band_width = bandw < 1 ? 8 : bandw;
-    *plain_bands = remap && remap[0] == 'b';
-}
+void mxk_last_gemm(mxk_last_gemm_t* out) { *out = g_last_gemm; }
 
-void mxk_last_gemm_group(int* problems, int64_t* blocks) {
-    *problems = g_last_gemm_group_problems;
-    *blocks = g_last_gemm_group_blocks;
-}
+const mx_gemm_knobs* mxk_gemm_knobs(void) { return &gemm_knobs(); }
 
 // One launch over the union of the tiles of plan's launched problems. The
 // device table goes into `ws` (plan.table_bytes() or more) on `stream`
@@ -894,48 +869,17 @@ int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
                        (size_t)(count + 1) * sizeof(int32_t),
                        hipMemcpyHostToDevice, stream) != hipSuccess)
         return -2;
-    static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
-    const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
-                      : loopenv[0] == 'p' ? 1 : -1;
     const unsigned blocks = (unsigned)plan->blocks();
-    const int band0 = plan->entries[0].band;
-    const mx_group_entry* table = (const mx_group_entry*)ws;
-    auto form = [&](auto t, auto beta) {
-        using T = decltype(t);
-        constexpr int BT = decltype(beta)::value;
-        auto l = [&](auto ta, auto tb) {
-            launch_gemm_grouped<T, BT, decltype(ta)::value,
-                                decltype(tb)::value>(
-                count, blocks, band0, table, loopsel, plan->pitch32, stream);
-        };
-        using one = std::integral_constant<int, 1>;
-        using zero = std::integral_constant<int, 0>;
-        if (trans_a && trans_b) l(one{}, one{});
-        else if (trans_a)       l(one{}, zero{});
-        else if (trans_b)       l(zero{}, one{});
-        else                    l(zero{}, zero{});
-    };
-    using one = std::integral_constant<int, 1>;
-    using zero = std::integral_constant<int, 0>;
-    if (is_fp32) { if (beta_one) form(float{}, one{}); else form(float{}, zero{}); }
-    else         { if (beta_one) form(double{}, one{}); else form(double{}, zero{}); }
-    return (int)hipGetLastError() == 0 ? 0 : -2;
-}
-
-void mxk_last_gemm_config(mx_gemm_cfg_t* out) { *out = g_last_gemm_cfg; }
-
-void mxk_last_gemm_loop(int* out) { *out = g_last_gemm_loop; }
-
-// Pitch contract of the GEMM kernels: every column start must stay
-// 16-byte aligned (global_load_lds moves 16-byte chunks; the fused
-// epilogue stores float4), and a pitch must cover its leading dimension.
-static inline bool pitch_ok(int64_t ld, int64_t rows, int64_t elems16) {
-    return ld >= rows && ld % elems16 == 0;
-}
-
-void mxk_last_gemm_op(int* trans_a, int* trans_b) {
-    *trans_a = g_last_gemm_op[0];
-    *trans_b = g_last_gemm_op[1];
+    const mx_gemm_variant v = mx_gemm_select_grouped(
+        gemm_knobs(), is_fp32, beta_one, trans_a, trans_b,
+        plan->entries[0].band, plan->pitch32);
+    record_launch(v);
+    g_last_gemm.group_problems = count;
+    g_last_gemm.group_blocks = blocks;
+    // the per-launch scalars are unused but for nbm, the entry count
+    const gemm_args g{0, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, count, 0, 0,
+                      nullptr, (const mx_group_entry*)ws};
+    return gemm_launch(v, blocks, g, stream);
 }
 
 // C (+)= op(A) * op(B). A transposed operand is the stored image of the
@@ -964,64 +908,14 @@ int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
         return 0;
     }
     if (M % 128 || N % 128 || K % 16) return -4;
-    int nbn = (int)(N / 128);
-    static const char* bandenv = getenv("MARLIN_GEMM_BAND");
-    int bandw = bandenv ? atoi(bandenv) : 8;
-    if (bandw < 1) bandw = 8;
-    int band = nbn < bandw ? nbn : bandw;
-    // default: supertiled bands; MARLIN_GEMM_REMAP=bands -> plain bands
-    static const char* remap = getenv("MARLIN_GEMM_REMAP");
-    if (remap && remap[0] == 'b') band = -band;
-    // configs: default BK=16/BM=128 2x256-thread blocks per CU (measured
-    // winner); MARLIN_GEMM_CFG=bk32 -> 512-thread BK=32; =bm256 -> 256x128
-    // tile / 512-thread (requires M % 256 == 0; halves DMA-per-flop and
-    // barrier rate at 1 block/CU).
-    static const char* cfg = getenv("MARLIN_GEMM_CFG");
-    bool bk32 = (K % 32 == 0) && cfg && cfg[0] == 'b' && cfg[1] == 'k';
-    bool bm256 = (M % 256 == 0) && !is_fp32 && cfg && cfg[0] == 'b' && cfg[1] == 'm';
-    // the transposed forms exist in the default geometry only
-    if (trans_a || trans_b) bk32 = bm256 = false;
-    // k-phase stagger mask (experiment; see kernel comment). 0 = off.
-    static const char* phenv = getenv("MARLIN_GEMM_PHASE");
-    int phase_mask = phenv ? atoi(phenv) : 0;
-    // k-loop, decided per variant by paired runs on one box
-    // (profiles/r03_pipelined_loop.md): the pipelined one-barrier loop
-    // won for every fp64 variant (+6.5% default, +6.2% bk32, +9.9%
-    // bm256) and for fp32 bk32 (+7.2%), and lost for fp32 BK=16 (-3.0%;
-    // presumably its 4 waves/SIMD already cover the loop top), which
-    // keeps the two-barrier loop. MARLIN_GEMM_LOOP=twobar / =pipe force
-    // one loop everywhere (paired comparisons, tests). A pitch so large
-    // that the pipelined loop's 32-bit per-lane DMA offsets (up to 15
-    // columns of B, 1 of A, plus one 1 KiB run; checked at the largest
-    // admitted pitch by tests/test_gemm_stage_layout.py) could overflow
-    // always takes the two-barrier loop. A transposed operand takes the other
-    // operand's offsets with its own pitch, so the one bound on both
-    // pitches covers every form.
-    static const char* loopenv = getenv("MARLIN_GEMM_LOOP");
-    const int loopsel = !loopenv ? -1 : loopenv[0] == 't' ? 0
-                      : loopenv[0] == 'p' ? 1 : -1;
-    const bool pitch32 = lda < ((int64_t)1 << 26) && ldb < ((int64_t)1 << 26);
-    const gemm_call g{M, N, K, A, lda, B, ldb, C, ldc, band, phase_mask,
-                      loopsel, pitch32, stream};
-    // form and geometry, per type and beta: the transposed forms exist in
-    // the default geometry only, bm256 for fp64 only (never set for fp32)
-    auto dispatch = [&](auto t, auto beta) {
-        using T = decltype(t);
-        constexpr int BT = decltype(beta)::value;
-        if (trans_a && trans_b) launch_gemm<T, BT, 16, 128, 2, 2, 1, 1>(g);
-        else if (trans_a)       launch_gemm<T, BT, 16, 128, 2, 2, 1, 0>(g);
-        else if (trans_b)       launch_gemm<T, BT, 16, 128, 2, 2, 0, 1>(g);
-        else if (bm256) {
-            if constexpr (sizeof(T) == 8) launch_gemm<T, BT, 16, 256, 4, 2>(g);
-        }
-        else if (bk32)          launch_gemm<T, BT, 32, 128, 2, 4>(g);
-        else                    launch_gemm<T, BT, 16, 128, 2, 2>(g);
-    };
-    using one = std::integral_constant<int, 1>;
-    using zero = std::integral_constant<int, 0>;
-    if (is_fp32) { if (beta_one) dispatch(float{}, one{}); else dispatch(float{}, zero{}); }
-    else         { if (beta_one) dispatch(double{}, one{}); else dispatch(double{}, zero{}); }
-    return (int)hipGetLastError() == 0 ? 0 : -2;
+    const mx_gemm_variant v = mx_gemm_select(gemm_knobs(), is_fp32, beta_one,
+                                             trans_a, trans_b, M, N, K, lda,
+                                             ldb);
+    record_launch(v);
+    const int64_t nbm = M / v.BM;
+    const gemm_args g{M, N, K, A, lda, B, ldb, C, ldc, (int)nbm, v.band,
+                      v.phase_mask, nullptr, nullptr};
+    return gemm_launch(v, (unsigned)(nbm * (N / 128)), g, stream);
 }
 
 int mxk_gemm(int is_fp32, int beta_one,
@@ -1044,16 +938,12 @@ int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K,
     // C/addC are N x M: float4 rows need ldc % 4 == 0 and ldc >= N
     if (!pitch_ok(lda, M, 4) || !pitch_ok(ldb, K, 4) || !pitch_ok(ldc, N, 4))
         return -4;
-    int nbm = (int)(M / 128), nbn = (int)(N / 128);
-    int band = nbn < 8 ? nbn : 8;
-    dim3 grid((unsigned)(nbm * nbn)), block(256);
-    // the fp32 default geometry on the two-barrier loop, supertiled bands,
-    // no k-phase stagger, whatever the MARLIN_GEMM_* knobs say
-    hipLaunchKernelGGL(
-        (gemm_mfma_kernel<float, 0, 16, 128, 2, 2, 0, 0, 0, EPI_TN_ADD>),
-        grid, block, 0, stream, M, N, K, A, lda, B, ldb, C, ldc, nbm, band,
-        0, addC, (const mx_group_entry*)nullptr);
-    return (int)hipGetLastError() == 0 ? 0 : -2;
+    // not recorded as the last launch (kernels.h)
+    const mx_gemm_variant v = mx_gemm_select_epilogue(N);
+    const int64_t nbm = M / 128;
+    const gemm_args g{M, N, K, A, lda, B, ldb, C, ldc, (int)nbm, v.band,
+                      v.phase_mask, addC, nullptr};
+    return gemm_launch(v, (unsigned)(nbm * (N / 128)), g, stream);
 }
 
 int mxk_fill_random(int is_fp32, void* buf, int64_t m, int64_t n, int64_t ld,

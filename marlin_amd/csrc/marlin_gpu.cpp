@@ -27,40 +27,7 @@
 #include "../../include/marlin_gpu.h"
 #include "gemm_op_layout.h"
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
-
-// kernels.hip launchers
-extern "C" {
-int mxk_gemm(int is_fp32, int beta_one, int64_t M, int64_t N, int64_t K,
-             const void* A, int64_t lda, const void* B, int64_t ldb,
-             void* C, int64_t ldc, hipStream_t stream);
-int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
-                int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-                const void* B, int64_t ldb, void* C, int64_t ldc,
-                hipStream_t stream);
-void mxk_last_gemm_op(int* trans_a, int* trans_b);
-int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K, const float* A,
-                          int64_t lda, const float* B, int64_t ldb, float* C,
-                          int64_t ldc, const float* addC, hipStream_t stream);
-int mxk_fill_random(int is_fp32, void* buf, int64_t m, int64_t n, int64_t ld,
-                    uint64_t seed, hipStream_t stream);
-int mxk_zero_pad(int is_fp32, void* buf, int64_t rows_total,
-                 int64_t cols_total, int64_t ld, int64_t m, int64_t n,
-                 hipStream_t stream);
-int mxk_map(int is_fp32, int op, int64_t n, const void* a, const void* b,
-            double scalar, void* c, hipStream_t stream);
-int mxk_sum(int is_fp32, int64_t n, const void* a, double* partials,
-            double* out, hipStream_t stream);
-int mxk_transpose(int is_fp32, int64_t m, int64_t n, const void* in,
-                  void* out, hipStream_t stream);
-int mxk_gemv(int is_fp32, int64_t m, int64_t n, int64_t lda, const void* A,
-             const void* x, double* partial, void* y, hipStream_t stream);
-void mxk_last_gemm_config(mx_gemm_cfg_t* out);
-void mxk_last_gemm_loop(int* out);
-void mxk_gemm_remap_knobs(int* band_width, int* plain_bands);
-void mxk_last_gemm_group(int* problems, int64_t* blocks);
-int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
-                     const mx_group_plan* plan, void* ws, hipStream_t stream);
-}
+#include "kernels.h"           // the kernels.hip launchers
 
 #define HIP_OK(x)                                                        \
   do {                                                                   \
@@ -96,6 +63,17 @@ int64_t mx_slab_len(int64_t total, int parts, int idx) {
 int64_t mx_slab_off(int64_t total, int parts, int idx) {
   int64_t bl = (total + parts - 1) / parts;
   return (int64_t)idx * bl;
+}
+
+// The C shard of grid position (prow, pcol) of an m x n product on a
+// pr x pc grid: its logical size and the padded size of its device image.
+struct shard_t {
+  int64_t mi, nj, mip, njp;
+};
+static shard_t local_shard(int64_t m, int64_t n, int pr, int pc, int prow,
+                           int pcol) {
+  const int64_t mi = mx_slab_len(m, pr, prow), nj = mx_slab_len(n, pc, pcol);
+  return {mi, nj, round_up(mi, 128), round_up(nj, 128)};
 }
 
 struct mx_ctx {
@@ -142,7 +120,8 @@ const char* mx_strerror(int code) {
   }
 }
 
-// destroys whatever streams/events a partially-initialised ctx created
+// destroys the streams/events a ctx created (a partially-initialised one
+// included) and the ctx itself
 static void ctx_teardown(mx_ctx* c) {
   for (int i = 0; i < 16; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -182,12 +161,7 @@ int mx_shutdown(mx_ctx* c) {
                      &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1],
                      &c->wsG})
     if (b->ptr) (void)hipFree(b->ptr);
-  for (int i = 0; i < 16; i++)
-    if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  if (c->s_gemm) (void)hipStreamDestroy(c->s_gemm);
-  if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
-  if (c->s_comm) (void)hipStreamDestroy(c->s_comm);
-  delete c;
+  ctx_teardown(c);
   return MX_OK;
 }
 
@@ -347,17 +321,18 @@ int mx_download2d_off(mx_ctx* c, void* dst, const mx_dbuf* src,
 }
 
 // ---------------------------------------------------------------------------
-// device-resident GEMM (padded pitches required)
-static int gemm_device(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
-                       int64_t k, int64_t n, const void* dA, int64_t lda,
-                       const void* dB, int64_t ldb, void* dC, int64_t ldc,
-                       int trans_a = 0, int trans_b = 0) {
-  if (m % 128 || n % 128 || k % 16) return MX_EINVAL;
-  HIP_OK(hipSetDevice(c->device));
+// A GEMM launcher's code (kernels.h) as a code of the ABI.
+static inline int launch_status(int rc) {
+  return rc == 0 ? MX_OK : rc == -4 ? MX_EINVAL : MX_EHIP;
+}
+
+// One timed launch: enqueue() puts the GEMM on s_gemm and returns the
+// launcher's code; the event pair around it is waited for and its time and
+// the launch added to the stats.
+template <class Enqueue>
+static int timed_gemm(mx_ctx* c, Enqueue&& enqueue) {
   HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  int rc = mxk_gemm_op(is_fp32, beta_one, trans_a, trans_b, m, n, k, dA, lda,
-                       dB, ldb, dC, ldc, c->s_gemm);
-  if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
+  if (int rc = enqueue()) return launch_status(rc);
   HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
   HIP_OK(hipEventSynchronize(c->ev[1]));
   float ms = 0;
@@ -365,6 +340,19 @@ static int gemm_device(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
   c->st.gemm_ms += ms;
   c->st.gemm_launches += 1;
   return MX_OK;
+}
+
+// device-resident GEMM (padded pitches required)
+static int gemm_device(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
+                       int64_t k, int64_t n, const void* dA, int64_t lda,
+                       const void* dB, int64_t ldb, void* dC, int64_t ldc,
+                       int trans_a = 0, int trans_b = 0) {
+  if (m % 128 || n % 128 || k % 16) return MX_EINVAL;
+  HIP_OK(hipSetDevice(c->device));
+  return timed_gemm(c, [&] {
+    return mxk_gemm_op(is_fp32, beta_one, trans_a, trans_b, m, n, k, dA, lda,
+                       dB, ldb, dC, ldc, c->s_gemm);
+  });
 }
 
 int mx_dgemm_device(mx_ctx* c, int64_t m, int64_t k, int64_t n,
@@ -458,11 +446,11 @@ int mx_gemm_device_grouped(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
                            int trans_b, int count,
                            const mx_gemm_problem_t* problems) {
   if (!c) return MX_EINVAL;
-  int band_width = 8, plain_bands = 0;
-  mxk_gemm_remap_knobs(&band_width, &plain_bands);
+  const mx_gemm_knobs* knobs = mxk_gemm_knobs();
   mx_group_plan& plan = c->group_plan;
-  int rc = mx_gemm_group_plan(is_fp32, beta_one, trans_a, trans_b, band_width,
-                              plain_bands, count, problems, &plan);
+  int rc = mx_gemm_group_plan(is_fp32, beta_one, trans_a, trans_b,
+                              knobs->band_width, knobs->plain_bands, count,
+                              problems, &plan);
   c->st = {};
   if (rc) return rc;
   c->st.flops = plan.flops;
@@ -477,40 +465,44 @@ int mx_gemm_device_grouped(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
     return MX_OK;
   }
   if ((rc = ensure(c, &c->wsG, plan.table_bytes()))) return rc;
-  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  rc = mxk_gemm_grouped(is_fp32, beta_one, trans_a, trans_b, &plan,
-                        c->wsG.ptr, c->s_gemm);
-  if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
-  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-  HIP_OK(hipEventSynchronize(c->ev[1]));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->st.gemm_ms += ms;
-  c->st.gemm_launches += 1;
-  return MX_OK;
+  return timed_gemm(c, [&] {
+    return mxk_gemm_grouped(is_fp32, beta_one, trans_a, trans_b, &plan,
+                            c->wsG.ptr, c->s_gemm);
+  });
+}
+
+// The mx_last_gemm_* entries: views of the one record kernels.hip keeps.
+static mxk_last_gemm_t last_gemm() {
+  mxk_last_gemm_t r;
+  mxk_last_gemm(&r);
+  return r;
 }
 
 int mx_last_gemm_group(mx_ctx* c, int* problems_launched, int64_t* blocks) {
   if (!c || !problems_launched || !blocks) return MX_EINVAL;
-  mxk_last_gemm_group(problems_launched, blocks);
+  const mxk_last_gemm_t r = last_gemm();
+  *problems_launched = r.group_problems;
+  *blocks = r.group_blocks;
   return MX_OK;
 }
 
 int mx_last_gemm_op(mx_ctx* c, int* trans_a, int* trans_b) {
   if (!c || !trans_a || !trans_b) return MX_EINVAL;
-  mxk_last_gemm_op(trans_a, trans_b);
+  const mxk_last_gemm_t r = last_gemm();
+  *trans_a = r.trans_a;
+  *trans_b = r.trans_b;
   return MX_OK;
 }
 
 int mx_last_gemm_config(mx_ctx* c, mx_gemm_cfg_t* out) {
   if (!c || !out) return MX_EINVAL;
-  mxk_last_gemm_config(out);
+  *out = last_gemm().cfg;
   return MX_OK;
 }
 
 int mx_last_gemm_loop(mx_ctx* c, int* out) {
   if (!c || !out) return MX_EINVAL;
-  mxk_last_gemm_loop(out);
+  *out = last_gemm().loop;
   return MX_OK;
 }
 
@@ -572,17 +564,12 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                               n * elem, m, hipMemcpyHostToDevice, c->s_gemm));
       dAdd = (const float*)c->wsPA[0].ptr;
     }
-    HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-    rc = mxk_sgemm_tn_epilogue(mp, np, kp, (const float*)c->wsA.ptr, mp,
-                               (const float*)c->wsB.ptr, kp,
-                               (float*)c->wsC.ptr, np, dAdd, c->s_gemm);
-    if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
-    HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-    HIP_OK(hipEventSynchronize(c->ev[1]));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->st.gemm_ms += ms;
-    c->st.gemm_launches += 1;
+    rc = timed_gemm(c, [&] {
+      return mxk_sgemm_tn_epilogue(mp, np, kp, (const float*)c->wsA.ptr, mp,
+                                   (const float*)c->wsB.ptr, kp,
+                                   (float*)c->wsC.ptr, np, dAdd, c->s_gemm);
+    });
+    if (rc) return rc;
     // C_out is n x m
     HIP_OK(hipMemcpy2DAsync(C, n * elem, c->wsC.ptr, np * elem, n * elem, m,
                             hipMemcpyDeviceToHost, c->s_gemm));
@@ -781,9 +768,8 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
                       int64_t k, int64_t n, void* dC, int64_t kb_max) {
   const int64_t elem = is_fp32 ? 4 : 8;
   const ncclDataType_t nty = is_fp32 ? ncclFloat32 : ncclFloat64;
-  const int64_t mi = mx_slab_len(m, g.pr, g.prow);
-  const int64_t nj = mx_slab_len(n, g.pc, g.pcol);
-  const int64_t mip = round_up(mi, 128), njp = round_up(nj, 128);
+  const shard_t sh = local_shard(m, n, g.pr, g.pc, g.prow, g.pcol);
+  const int64_t nj = sh.nj, mip = sh.mip, njp = sh.njp;
   // Empty local shard (e.g. m < pr on tiny inputs): the reference path
   // handles any size, so this rank must still take part in every panel
   // broadcast (counts are uniform per row/col comm: mip is shared by the
@@ -852,7 +838,7 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
       HIP_OK(hipEventRecord(g0, c->s_gemm));
       rc = mxk_gemm(is_fp32, beta, mip, njp, kbp, pa, mip, pb, kbp, dC, mip,
                     c->s_gemm);
-      if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
+      if (rc) return launch_status(rc);
       c->st.gemm_launches += 1;
       HIP_OK(hipEventRecord(g1, c->s_gemm));
       gemm_tv.push_back({g0, g1});
@@ -952,26 +938,17 @@ static int summa_kres_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
                              void* dC) {
   if (!c->have_comm) return MX_ENOCOMM;
   const int64_t elem = is_fp32 ? 4 : 8;
-  const int64_t mi = mx_slab_len(m, c->pr, c->prow);
-  const int64_t nj = mx_slab_len(n, c->pc, c->pcol);
-  const int64_t mip = round_up(mi, 128), njp = round_up(nj, 128);
+  const shard_t s = local_shard(m, n, c->pr, c->pc, c->prow, c->pcol);
   const int64_t kp = round_up(k, 16);
   c->st = {};
   c->st.flops = 2.0 * m * k * n;
   c->st.bytes_moved = (double)elem * (m * k + k * n + m * n);
-  if (mip == 0 || njp == 0) return MX_OK;  // empty shard: nothing to do
+  if (s.mip == 0 || s.njp == 0) return MX_OK;  // empty shard: nothing to do
   HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  int rc = mxk_gemm(is_fp32, 0, mip, njp, kp, dA, mip, dB, kp, dC, mip,
-                    c->s_gemm);
-  if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
-  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-  HIP_OK(hipEventSynchronize(c->ev[1]));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->st.gemm_ms += ms;
-  c->st.gemm_launches += 1;
-  return MX_OK;
+  return timed_gemm(c, [&] {
+    return mxk_gemm(is_fp32, 0, s.mip, s.njp, kp, dA, s.mip, dB, kp, dC,
+                    s.mip, c->s_gemm);
+  });
 }
 
 int mx_gemm_summa_kres_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
@@ -988,9 +965,8 @@ static int summa_kres_host(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
   if (!c || !A || !B || !C) return MX_EINVAL;
   if (!c->have_comm) return MX_ENOCOMM;
   const int64_t elem = is_fp32 ? 4 : 8;
-  const int64_t mi = mx_slab_len(m, c->pr, c->prow);
-  const int64_t nj = mx_slab_len(n, c->pc, c->pcol);
-  const int64_t mip = round_up(mi, 128), njp = round_up(nj, 128);
+  const auto [mi, nj, mip, njp] =
+      local_shard(m, n, c->pr, c->pc, c->prow, c->pcol);
   const int64_t kp = round_up(k, 16);
   if (mi == 0 || nj == 0) return MX_OK;
   int rc;
@@ -1040,11 +1016,10 @@ static int summa_host(mx_ctx* c, int is_fp32, int64_t m, int64_t k, int64_t n,
   if (!c || !A || !B || !C) return MX_EINVAL;
   if (!c->have_comm) return MX_ENOCOMM;
   const int64_t elem = is_fp32 ? 4 : 8;
-  const int64_t mi = mx_slab_len(m, c->pr, c->prow);
-  const int64_t nj = mx_slab_len(n, c->pc, c->pcol);
+  const auto [mi, nj, mip, njp] =
+      local_shard(m, n, c->pr, c->pc, c->prow, c->pcol);
   const int64_t kaj = mx_slab_len(k, c->pc, c->pcol);
   const int64_t kbi = mx_slab_len(k, c->pr, c->prow);
-  const int64_t mip = round_up(mi, 128), njp = round_up(nj, 128);
   const int64_t kbi_p = round_up(kbi, 16);
   int rc;
   HIP_OK(hipSetDevice(c->device));
@@ -1203,19 +1178,12 @@ int mx_sgemm_epilogue_device(mx_ctx* c, int64_t m, int64_t k, int64_t n,
   c->st.flops = 2.0 * m * k * n;
   c->st.bytes_moved = 4.0 * (m * k + k * n + m * n + (dAdd ? m * n : 0));
   HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  int rc = mxk_sgemm_tn_epilogue(m, n, k, (const float*)dA->ptr, lda,
-                                 (const float*)dB->ptr, ldb, (float*)dC->ptr,
-                                 ldc, dAdd ? (const float*)dAdd->ptr : nullptr,
-                                 c->s_gemm);
-  if (rc) return rc == -4 ? MX_EINVAL : MX_EHIP;
-  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-  HIP_OK(hipEventSynchronize(c->ev[1]));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->st.gemm_ms += ms;
-  c->st.gemm_launches += 1;
-  return MX_OK;
+  return timed_gemm(c, [&] {
+    return mxk_sgemm_tn_epilogue(
+        m, n, k, (const float*)dA->ptr, lda, (const float*)dB->ptr, ldb,
+        (float*)dC->ptr, ldc, dAdd ? (const float*)dAdd->ptr : nullptr,
+        c->s_gemm);
+  });
 }
 
 // Failure-injection probe (RCCL error codes surfaced through

@@ -148,8 +148,9 @@ def config_cases(env):
 
 
 def expected_config(env, c):
-    """Restatement of the launcher's variant selection (mxk_gemm): what
-    mx_last_gemm_config must report for case c under env."""
+    """Restatement of the launcher's variant selection (mx_gemm_select of
+    gemm_launch_policy.h; test_gemm_launch_policy.py compares the two on
+    the CPU): what mx_last_gemm_config must report for case c under env."""
     cfg = env.get("MARLIN_GEMM_CFG", "")
     bk32 = cfg.startswith("bk") and c.K % 32 == 0
     bm256 = cfg.startswith("bm") and not c.fp32 and c.M % 256 == 0
