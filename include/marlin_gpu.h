@@ -279,6 +279,56 @@ int mx_gemm_device_grouped(mx_ctx* ctx, int is_fp32, int beta_one,
  * recent grouped launch in this process; zeros before the first. */
 int mx_last_gemm_group(mx_ctx* ctx, int* problems_launched, int64_t* blocks);
 
+/* Split-K GEMM: C (+)= op(A)·op(B) with k cut into S slices that run as S
+ * times as many blocks, for products whose m/128 x n/128 tiles alone leave
+ * the GPU idle (a tall-skinny Gram matrix, a small C with a long k).
+ *
+ * Arguments and pitch contract are mx_gemm_device_op's, empty shapes too
+ * (m == 0 or n == 0 is a no-op, k == 0 clears C unless accumulating). In
+ * addition every region must fit its buffer and C must be disjoint from A
+ * and B, by the rules of mx_gemm_device_grouped (dA == dB stays allowed).
+ * Everything is checked before anything is enqueued or allocated: a
+ * refused call returns MX_EINVAL and touches no buffer.
+ *
+ * slices: 0 = auto, 1 = do not split, >= 2 = that many, clamped to k / 16;
+ * < 0 is MX_EINVAL. Auto (gemm_splitk_plan.h) keeps S = 1 when the tiles
+ * already reach its fill target (measured: one block per CU in fp64, two
+ * in fp32, half of what the device holds) and otherwise cuts k until
+ * S * tiles reaches it, never leaving a slice fewer than
+ * MX_SPLITK_MIN_KSTEPS k-steps of 16.
+ *
+ * Effective S == 1 is the launch of mx_gemm_device_op, bit for bit, with
+ * no workspace. For S >= 2 slice s covers the k-steps [start_s, start_s +
+ * len_s) of 16: contiguous, ascending, lengths differing by at most one
+ * step, the longer slices first. The slices run as ONE grouped launch, a
+ * second kernel on the same stream then adds the partial products in
+ * ascending slice order with plain adds in the element type:
+ *     beta_one == 0:  C = ((P_0 + P_1) + P_2) + ...
+ *     beta_one == 1:  C = (((C + P_0) + P_1) + P_2) + ...
+ * where P_s is bit for bit what mx_gemm_device_op (beta 0) returns on
+ * slice s alone. The result therefore depends on S, but for a given S not
+ * on the schedule, the device's load or the run: no atomics are involved.
+ * Partial products live in a workspace the context owns (tight m x n
+ * slabs; S - 1 of them, slice 0 going straight into C, or S when
+ * accumulating), grown on demand and freed by mx_shutdown; auto never needs
+ * more than 64 MiB of it. Rows [m, ldc) of C are neither read nor written.
+ *
+ * The grouped entry's limits apply: the default kernel geometry only,
+ * MARLIN_GEMM_LOOP, _BAND and _REMAP honoured, _CFG and _PHASE not, one
+ * pitch of 2^26 elements or more puts the launch on the two-barrier loop.
+ * Stats: flops = 2mkn, gemm_launches = 1, gemm_ms = event time over the
+ * GEMM and the reduce. mx_last_gemm_group reports (S, S * tiles),
+ * mx_last_gemm_config, _op and _loop the grouped launch (beta_one = 0 even
+ * when accumulating: the accumulation happens in the reduce). */
+int mx_gemm_device_splitk(mx_ctx* ctx, int is_fp32, int beta_one, int trans_a,
+                          int trans_b, int64_t m, int64_t k, int64_t n,
+                          const mx_dbuf* dA, int64_t lda,
+                          const mx_dbuf* dB, int64_t ldb,
+                          mx_dbuf* dC, int64_t ldc, int slices);
+/* Effective S and workspace bytes used by the most recent split-K call in
+ * this process: (1, 0) after an unsplit one, (0, 0) before the first. */
+int mx_last_gemm_splitk(mx_ctx* ctx, int* slices, int64_t* workspace_bytes);
+
 /* Introspection: the gemm_mfma_kernel instantiation and remap arguments
  * of the most recent plain GEMM launch in this process (any entry that
  * reaches the kernel launcher; all zero before the first launch). The

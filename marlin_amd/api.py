@@ -284,9 +284,11 @@ class DenseVecMatrix:
         dXT.free()
         return w
 
-    def computeGramianMatrix(self):
+    def computeGramianMatrix(self, split_k=None):
         """DenseVecMatrix.computeGramianMatrix (DenseVecMatrix.scala:1464):
-        the local Gram matrix A^T A (device-resident compute)."""
+        the local Gram matrix A^T A (device-resident compute). split_k is
+        Engine.gemm_dd's: "auto" or a slice count cuts the long row
+        dimension across blocks (a tall-skinny A has few C tiles)."""
         n = self.numCols()
         if n > 65535:
             raise ValueError(f"Argument with more than 65535 cols: {n}")
@@ -294,7 +296,7 @@ class DenseVecMatrix:
         dA = eng.upload_matrix(self._host())
         # A^T·A on the one resident image: the kernel stages the
         # transposed operand itself, so no transposed copy is held
-        G = eng.gemm_dd(dA, dA, trans_a=True)
+        G = eng.gemm_dd(dA, dA, trans_a=True, split_k=split_k)
         out = eng.download_matrix(G)
         for d in (dA, G):
             d.free()

@@ -15,17 +15,21 @@
 // mx_last_gemm_* entries): the env knobs are latched per process, so a test
 // can only prove which instantiation it exercised by reading this back. A
 // grouped launch writes every field, a plain one leaves the group fields
-// alone, mxk_sgemm_tn_epilogue writes nothing.
+// alone, mxk_sgemm_tn_epilogue writes nothing. The split-K fields are the
+// split-K entry's alone (mxk_note_splitk): no launcher touches them.
 struct mxk_last_gemm_t {
   mx_gemm_cfg_t cfg;
   int loop;                 // 0 = two-barrier, 1 = pipelined
   int trans_a, trans_b;     // op(A), op(B): 1 = transposed
   int group_problems;       // last grouped launch: problems that ran
   int64_t group_blocks;     //                      and its grid size
+  int splitk_slices;        // last split-K call: effective S (1 = unsplit)
+  int64_t splitk_ws_bytes;  //                    and workspace it used
 };
 
 extern "C" {
 void mxk_last_gemm(mxk_last_gemm_t* out);
+void mxk_note_splitk(int slices, int64_t workspace_bytes);
 // the latched MARLIN_GEMM_* knobs (what the grouped plan's bands need)
 const mx_gemm_knobs* mxk_gemm_knobs(void);
 
@@ -38,6 +42,10 @@ int mxk_gemm_op(int is_fp32, int beta_one, int trans_a, int trans_b,
                 hipStream_t stream);
 int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
                      const mx_group_plan* plan, void* ws, hipStream_t stream);
+// C (m x n, pitch ldc) += W_0 + ... + W_{nslabs-1} as a left fold in the
+// element type; slab j is the tight m x n image at W + j * m * n.
+int mxk_splitk_reduce(int is_fp32, int64_t m, int64_t n, void* C, int64_t ldc,
+                      const void* W, int nslabs, hipStream_t stream);
 int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K, const float* A,
                           int64_t lda, const float* B, int64_t ldb, float* C,
                           int64_t ldc, const float* addC, hipStream_t stream);

@@ -780,6 +780,58 @@ __global__ void gemv_reduce_kernel(int64_t m, int nchunks,
 }
 
 // ---------------------------------------------------------------------------
+// Split-K combine (mx_gemm_device_splitk): C += W_0 + W_1 + ... as a left
+// fold, ((C + W_0) + W_1) + ..., in the element type. C is m x n at pitch
+// ldc and already holds the first term (slice 0's product, or the caller's
+// C when accumulating, which is why one kernel serves both betas); slab j
+// is the tight m x n partial product at W + j * slab. It runs as its own
+// launch behind the GEMM on the same stream, so stream order alone makes
+// the partials visible: no fence, counter or atomic, and the order of the
+// adds is the slice order whatever the schedule, so the bits are fixed.
+// HBM-bound: one thread per 16-byte chunk of a C column (m is a multiple
+// of 128, so a chunk never crosses into the pad rows [m, ldc), which are
+// neither read nor written), capped grid, grid-stride. The slab loads of a
+// chunk are independent and issued eight at a time ahead of their adds.
+// They are nontemporal: a partial is read exactly once, and loading it
+// without keeping it cached measured 6.2-6.8 TB/s inside the entry against
+// 4.4-4.9 for plain loads at 4 and 8 slices of a 4096^2 fp64 C, and the
+// same at 2 slices (profiles/gemm_splitk.md).
+typedef double v2d __attribute__((ext_vector_type(2)));
+template <typename T> struct chunk16_t;
+template <> struct chunk16_t<double> { using type = v2d; };
+template <> struct chunk16_t<float>  { using type = v4f; };
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+splitk_reduce_kernel(T* __restrict__ C, int64_t ldc, int64_t m, int64_t n,
+                     const T* __restrict__ W, int64_t slab, int nslabs) {
+    using V = typename chunk16_t<T>::type;
+    constexpr int64_t E = 16 / sizeof(T);
+    const int64_t per_col = m / E, total = per_col * n;
+    const int64_t slab_v = slab / E;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        const int64_t col = i / per_col, r = i - col * per_col;
+        V* cp = reinterpret_cast<V*>(C + col * ldc) + r;
+        const V* wp = reinterpret_cast<const V*>(W) + i;   // tight: linear
+        V acc = *cp;
+        int j = 0;
+        for (; j + 8 <= nslabs; j += 8) {
+            V w[8];
+            #pragma unroll
+            for (int b = 0; b < 8; b++)
+                w[b] = __builtin_nontemporal_load(&wp[(j + b) * slab_v]);
+            #pragma unroll
+            for (int b = 0; b < 8; b++) acc = acc + w[b];   // ascending
+        }
+        for (; j < nslabs; j++)
+            acc = acc + __builtin_nontemporal_load(&wp[j * slab_v]);
+        *cp = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GEMM launch. Which instantiation a call runs is decided in
 // gemm_launch_policy.h; here are the latched knobs, the record of the last
 // launch, the one step from a selected variant to its compiled kernel, and
@@ -848,6 +900,34 @@ static int gemm_launch(const mx_gemm_variant& v, unsigned blocks,
 extern "C" {
 
 void mxk_last_gemm(mxk_last_gemm_t* out) { *out = g_last_gemm; }
+
+void mxk_note_splitk(int slices, int64_t workspace_bytes) {
+    g_last_gemm.splitk_slices = slices;
+    g_last_gemm.splitk_ws_bytes = workspace_bytes;
+}
+
+// m a positive multiple of 128 and ldc one of 16 bytes are the GEMM
+// entries' contract (checked again: the 16-byte chunks rely on both).
+int mxk_splitk_reduce(int is_fp32, int64_t m, int64_t n, void* C, int64_t ldc,
+                      const void* W, int nslabs, hipStream_t stream) {
+    const int64_t e16 = is_fp32 ? 4 : 2;
+    if (m <= 0 || n <= 0 || m % 128 || nslabs < 1 || !C || !W) return -4;
+    if (!pitch_ok(ldc, m, e16)) return -4;
+    // memory-bound idiom: a capped grid (16 blocks per CU), grid-stride the
+    // rest
+    const int64_t chunks = m / e16 * n;
+    const int64_t want = (chunks + 255) / 256;
+    const dim3 grid((unsigned)(want < 4096 ? want : 4096)), block(256);
+    if (is_fp32)
+        hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, block, 0, stream,
+                           (float*)C, ldc, m, n, (const float*)W, m * n,
+                           nslabs);
+    else
+        hipLaunchKernelGGL(splitk_reduce_kernel<double>, grid, block, 0,
+                           stream, (double*)C, ldc, m, n, (const double*)W,
+                           m * n, nslabs);
+    return (int)hipGetLastError() == 0 ? 0 : -2;
+}
 
 const mx_gemm_knobs* mxk_gemm_knobs(void) { return &gemm_knobs(); }
 

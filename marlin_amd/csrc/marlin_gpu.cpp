@@ -27,6 +27,7 @@
 #include "../../include/marlin_gpu.h"
 #include "gemm_op_layout.h"
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
+#include "gemm_splitk_plan.h"  // the split-K slicing policy
 #include "kernels.h"           // the kernels.hip launchers
 
 #define HIP_OK(x)                                                        \
@@ -92,6 +93,12 @@ struct mx_ctx {
   // grouped GEMM: the device table's staging buffer and its host image
   mx_dbuf wsG;
   mx_group_plan group_plan;
+  // split-K GEMM: the partial products (tight m x n slabs), the slice table
+  // handed to the grouped plan, and the CU count the auto policy reads
+  mx_dbuf wsK;
+  std::vector<mx_splitk_slice> splitk_slices;
+  std::vector<mx_gemm_problem_t> splitk_rows;
+  int cus = 0;
   mx_stats_t st = {};
 };
 
@@ -159,7 +166,7 @@ int mx_shutdown(mx_ctx* c) {
   if (c->world) ncclCommDestroy(c->world);
   for (mx_dbuf* b : {&c->wsA, &c->wsB, &c->wsC,
                      &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1],
-                     &c->wsG})
+                     &c->wsG, &c->wsK})
     if (b->ptr) (void)hipFree(b->ptr);
   ctx_teardown(c);
   return MX_OK;
@@ -471,6 +478,87 @@ int mx_gemm_device_grouped(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
   });
 }
 
+// One product with k cut into slices (include/marlin_gpu.h): the slices
+// run as one grouped launch of beta-0 problems, slice 0 straight into C
+// (when not accumulating) and the rest into tight slabs of wsK; the reduce
+// kernel then folds the slabs into C in slice order on the same stream.
+int mx_gemm_device_splitk(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
+                          int trans_b, int64_t m, int64_t k, int64_t n,
+                          const mx_dbuf* dA, int64_t lda, const mx_dbuf* dB,
+                          int64_t ldb, mx_dbuf* dC, int64_t ldc, int slices) {
+  if (!c || !dA || !dB || !dC) return MX_EINVAL;
+  c->st = {};
+  if (slices < 0) return MX_EINVAL;
+  // The whole product as a table of one: the pitch contract, every region
+  // inside its buffer, C disjoint from A and B. The slices are sub-regions
+  // of these, so what passes here passes slice by slice.
+  const mx_gemm_knobs* knobs = mxk_gemm_knobs();
+  mx_group_plan& plan = c->group_plan;
+  const mx_gemm_problem_t whole = {m, k, n, dA, 0, lda, dB, 0, ldb,
+                                   dC, 0, ldc};
+  int rc = mx_gemm_group_plan(is_fp32, beta_one, trans_a, trans_b,
+                              knobs->band_width, knobs->plain_bands, 1, &whole,
+                              &plan);
+  if (rc) return rc;
+  c->st.flops = 2.0 * m * k * n;
+  if (m == 0 || n == 0) {               // empty: nothing to do
+    mxk_note_splitk(1, 0);
+    return MX_OK;
+  }
+  HIP_OK(hipSetDevice(c->device));
+  int S = slices;
+  if (S == 0) {
+    if (c->cus == 0)
+      HIP_OK(hipDeviceGetAttribute(&c->cus,
+                                   hipDeviceAttributeMultiprocessorCount,
+                                   c->device));
+    S = mx_splitk_auto(is_fp32, m, n, k, c->cus);
+  }
+  S = mx_splitk_slices(k, S, nullptr);
+  if (S == 1) {                         // the plain entry's launch (k == 0 too)
+    rc = gemm_device(c, is_fp32, beta_one, m, k, n, dA->ptr, lda, dB->ptr,
+                     ldb, dC->ptr, ldc, trans_a, trans_b);
+    if (rc == MX_OK) mxk_note_splitk(1, 0);
+    return rc;
+  }
+
+  const int64_t elem = is_fp32 ? 4 : 8;
+  const int64_t slab = m * n;           // fits: the C region fits its buffer
+  const int nslabs = beta_one ? S : S - 1;
+  if (nslabs > INT64_MAX / (slab * elem)) return MX_ENOMEM;
+  const int64_t ws_bytes = nslabs * slab * elem;
+  if ((rc = ensure(c, &c->wsK, ws_bytes))) return rc;
+  c->splitk_slices.resize((size_t)S);
+  mx_splitk_slices(k, S, c->splitk_slices.data());
+  c->splitk_rows.clear();
+  for (int s = 0; s < S; s++) {
+    const int64_t k0 = c->splitk_slices[s].start * 16;
+    mx_gemm_problem_t q = {m, c->splitk_slices[s].len * 16, n,
+                           dA, trans_a ? k0 : k0 * lda, lda,
+                           dB, trans_b ? k0 * ldb : k0, ldb,
+                           dC, 0, ldc};
+    if (beta_one || s > 0) {
+      q.dC = &c->wsK;
+      q.c_off = (beta_one ? s : s - 1) * slab;
+      q.ldc = m;
+    }
+    c->splitk_rows.push_back(q);
+  }
+  rc = mx_gemm_group_plan(is_fp32, 0, trans_a, trans_b, knobs->band_width,
+                          knobs->plain_bands, S, c->splitk_rows.data(), &plan);
+  if (rc) return rc;
+  if ((rc = ensure(c, &c->wsG, plan.table_bytes()))) return rc;
+  rc = timed_gemm(c, [&] {
+    if (int e = mxk_gemm_grouped(is_fp32, 0, trans_a, trans_b, &plan,
+                                 c->wsG.ptr, c->s_gemm))
+      return e;
+    return mxk_splitk_reduce(is_fp32, m, n, dC->ptr, ldc, c->wsK.ptr, nslabs,
+                             c->s_gemm);
+  });
+  if (rc == MX_OK) mxk_note_splitk(S, ws_bytes);   // only a split that ran
+  return rc;
+}
+
 // The mx_last_gemm_* entries: views of the one record kernels.hip keeps.
 static mxk_last_gemm_t last_gemm() {
   mxk_last_gemm_t r;
@@ -483,6 +571,14 @@ int mx_last_gemm_group(mx_ctx* c, int* problems_launched, int64_t* blocks) {
   const mxk_last_gemm_t r = last_gemm();
   *problems_launched = r.group_problems;
   *blocks = r.group_blocks;
+  return MX_OK;
+}
+
+int mx_last_gemm_splitk(mx_ctx* c, int* slices, int64_t* workspace_bytes) {
+  if (!c || !slices || !workspace_bytes) return MX_EINVAL;
+  const mxk_last_gemm_t r = last_gemm();
+  *slices = r.splitk_slices;
+  *workspace_bytes = r.splitk_ws_bytes;
   return MX_OK;
 }
 

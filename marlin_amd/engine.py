@@ -155,6 +155,10 @@ def _load():
         "mx_gemm_device_grouped": (ctypes.c_int, [vp] + [ctypes.c_int] * 5
                                    + [P(MxGemmProblem)]),
         "mx_last_gemm_group": (ctypes.c_int, [vp, P(ctypes.c_int), P(i64)]),
+        "mx_gemm_device_splitk": (ctypes.c_int, [vp] + [ctypes.c_int] * 4
+                                  + [i64, i64, i64, vp, i64, vp, i64, vp, i64,
+                                     ctypes.c_int]),
+        "mx_last_gemm_splitk": (ctypes.c_int, [vp, P(ctypes.c_int), P(i64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -639,14 +643,17 @@ class Engine:
         return DeviceMatrix(self, out, dm.n, dm.m, ncap, dm.fp32)
 
     def gemm_dd(self, A, B, C=None, accumulate=False, trans_a=False,
-                trans_b=False):
+                trans_b=False, split_k=None):
         """Device-resident C (+)= op(A) @ op(B) on cached matrices, op(X)
         = X^T where trans_x: a transposed operand is used as stored, no
         transposed copy is made. A DeviceMatrix image has its pitch and
         its column capacity padded to 128 with zero pads, so every form
         runs on the padded dims and stays exact; C is a DeviceMatrix with
         the logical shape of the product, pitch roundup(m, 128), and
-        zero pads (it can feed the next GEMM in any role)."""
+        zero pads (it can feed the next GEMM in any role).
+        split_k=None is the plain entry; "auto" or an int runs
+        mx_gemm_device_splitk with slices = 0 or that int (k cut into
+        slices that run as one launch, summed in slice order)."""
         assert A.fp32 == B.fp32
         m, k, n = gemm_op_shape((A.m, A.n), (B.m, B.n), trans_a, trans_b)
         mp = (m + 127) // 128 * 128      # A.pitch, or A's column capacity
@@ -661,6 +668,13 @@ class Engine:
         # stored rows rounded to 128 (>= kp where k runs along the rows)
         assert A.pitch >= (kp if trans_a else mp)
         assert B.pitch >= (np_ if trans_b else kp)
+        if split_k is not None:
+            self.gemm_splitk_raw(mp, kp, np_, A.buf, A.pitch, B.buf, B.pitch,
+                                 C.buf, C.pitch,
+                                 0 if split_k == "auto" else int(split_k),
+                                 A.fp32, accumulate, 1 if trans_a else 0,
+                                 1 if trans_b else 0)
+            return C
         _ck(lib().mx_gemm_device_op(self._ctx, 1 if A.fp32 else 0,
                                     1 if accumulate else 0,
                                     1 if trans_a else 0, 1 if trans_b else 0,
@@ -668,6 +682,28 @@ class Engine:
                                     B.buf, B.pitch, C.buf, C.pitch),
             "mx_gemm_device_op")
         return C
+
+    def gemm_splitk_raw(self, m, k, n, dA, lda, dB, ldb, dC, ldc, slices=0,
+                        fp32=False, accumulate=False, trans_a=0, trans_b=0,
+                        check=True):
+        """mx_gemm_device_splitk on raw device buffers: padded dims,
+        pitches in elements, slices 0 = auto, 1 = unsplit, >= 2 explicit.
+        Returns the entry's code; check=True raises on a non-zero one."""
+        rc = lib().mx_gemm_device_splitk(
+            self._ctx, 1 if fp32 else 0, 1 if accumulate else 0, int(trans_a),
+            int(trans_b), m, k, n, dA, lda, dB, ldb, dC, ldc, int(slices))
+        if check:
+            _ck(rc, "mx_gemm_device_splitk")
+        return rc
+
+    def last_gemm_splitk(self):
+        """(effective slices, workspace bytes) of the last split-K call:
+        (1, 0) after an unsplit one, (0, 0) before the first."""
+        s, ws = ctypes.c_int(-1), ctypes.c_int64(-1)
+        _ck(lib().mx_last_gemm_splitk(self._ctx, ctypes.byref(s),
+                                      ctypes.byref(ws)),
+            "mx_last_gemm_splitk")
+        return s.value, ws.value
 
     def gemm_grouped_raw(self, problems, fp32=False, accumulate=False,
                          trans_a=False, trans_b=False, check=True):
