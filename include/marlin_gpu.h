@@ -157,11 +157,22 @@ int mx_tile_dgemm_acc(mx_ctx* ctx, int64_t tm, int64_t tk, int64_t tn,
 typedef struct mx_dbuf mx_dbuf;          /* opaque device buffer            */
 int mx_alloc(mx_ctx* ctx, int64_t bytes, mx_dbuf** out);
 int mx_free(mx_ctx* ctx, mx_dbuf* buf);
+/* Argument contract of the auxiliary device-buffer entries (the transfers,
+ * mx_fill_random, mx_zero_pad, mx_transpose_device, mx_dgemv_device and
+ * mx_map; marlin_amd/csrc/aux_guards.h is the code): every argument is
+ * checked before the device is selected or anything is enqueued, a
+ * violation returns MX_EINVAL and has touched no buffer, and an extent is
+ * compared with the size the buffer was allocated with, overflow-safely. */
+/* Whole-buffer transfers: 0 <= bytes <= the buffer's size. */
 int mx_upload(mx_ctx* ctx, mx_dbuf* dst, const void* src, int64_t bytes);
 int mx_download(mx_ctx* ctx, void* dst, const mx_dbuf* src, int64_t bytes);
-/* Fill a device fp64 buffer with the deterministic xorshift64* U[0,1)
- * stream (the randomDenVecMatrix stand-in, MTUtils.scala:63-73 semantics:
- * seeded, per-element reproducible). */
+/* Fill the first n_elems elements of a device buffer, fp64 (is_fp32 = 0)
+ * or fp32, with the deterministic U[0,1) stream of the randomDenVecMatrix
+ * stand-in (MTUtils.scala:63-73 semantics: seeded, per-element
+ * reproducible): element i is splitmix64(seed + (i+1) * 0x9E3779B97F4A7C15,
+ * wrapping) >> 11, times 2^-53, and in fp32 that double rounded to nearest.
+ * n_elems >= 0 and n_elems * elem <= the buffer's size, else MX_EINVAL;
+ * n_elems == 0 is MX_OK and launches nothing. */
 int mx_fill_random(mx_ctx* ctx, mx_dbuf* buf, int64_t n_elems,
                    uint64_t seed, int is_fp32);
 /* Device-resident GEMM on padded-pitch device buffers created by the
@@ -187,12 +198,21 @@ int mx_sgemm_device(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,
                     const mx_dbuf* dB, int64_t ldb,
                     mx_dbuf* dC, int64_t ldc);
 /* 2D pitched transfers + zeroing for device-resident matrices (the
- * RDD.cache() analog) and a beta-capable device GEMM. */
+ * RDD.cache() analog) and a beta-capable device GEMM.
+ * The pitched transfers move a tight host m x n image to or from the
+ * device image of pitch pitch_elems: elem is 4 or 8, m and n >= 1,
+ * pitch_elems >= m, and the (n-1) * pitch_elems + m elements of the device
+ * region fit the buffer, else MX_EINVAL. */
 int mx_upload2d(mx_ctx* ctx, mx_dbuf* dst, int64_t pitch_elems,
                 const void* src, int64_t m, int64_t n, int elem);
 int mx_download2d(mx_ctx* ctx, void* dst, const mx_dbuf* src,
                   int64_t pitch_elems, int64_t m, int64_t n, int elem);
+/* Zero the first bytes of the buffer: 0 <= bytes <= its size. */
 int mx_memset(mx_ctx* ctx, mx_dbuf* buf, int64_t bytes);
+/* out[n x m] = in[m x n]^T, both tight col-major device images. m, n >= 0
+ * (either zero is a no-op MX_OK), m * n elements fit both buffers, and in
+ * is not out, in handle or in device pointer (the kernel is out of place),
+ * else MX_EINVAL. Elements beyond the first m * n of out are not written. */
 int mx_transpose_device(mx_ctx* ctx, int is_fp32, int64_t m, int64_t n,
                         const mx_dbuf* in, mx_dbuf* out);
 int mx_gemm_device_ex(mx_ctx* ctx, int is_fp32, int beta_one, int64_t m,
@@ -395,7 +415,12 @@ int mx_gemm_summa_virtual(mx_ctx* ctx, int is_fp32, int pr, int pc, int prow,
 
 /* Restore the zero-pad invariant of a rows_total x cols_total padded
  * image (pitch ld) whose logical content is m x n: pads outside m x n
- * are zeroed (used after mx_fill_random of a whole padded buffer). */
+ * are zeroed (used after mx_fill_random of a whole padded buffer); the
+ * m x n interior, rows [rows_total, ld) and everything past column
+ * cols_total are not written. 0 <= m <= rows_total <= ld, 0 <= n <=
+ * cols_total, and the (cols_total-1) * ld + rows_total elements of the
+ * image fit the buffer, else MX_EINVAL; an empty image (rows_total or
+ * cols_total == 0) is a no-op MX_OK. */
 int mx_zero_pad(mx_ctx* ctx, mx_dbuf* buf, int64_t rows_total,
                 int64_t cols_total, int64_t ld, int64_t m, int64_t n,
                 int is_fp32);
@@ -405,7 +430,8 @@ int mx_zero_pad(mx_ctx* ctx, mx_dbuf* buf, int64_t rows_total,
 int mx_download_off(mx_ctx* ctx, void* dst, const mx_dbuf* src,
                     int64_t off_bytes, int64_t bytes);
 /* Pitched download starting at a byte offset (one ROW of a col-major
- * image: off = i * elem, m = 1, n = cols, pitch = ld). */
+ * image: off = i * elem, m = 1, n = cols, pitch = ld). The contract of
+ * mx_download2d, with off_bytes >= 0 and the region counted from there. */
 int mx_download2d_off(mx_ctx* ctx, void* dst, const mx_dbuf* src,
                       int64_t off_bytes, int64_t pitch_elems, int64_t m,
                       int64_t n, int elem);
@@ -434,6 +460,9 @@ int mx_test_rccl_error(mx_ctx* ctx);
 #define MX_OP_MULS  6   /* C = A * s          (multiply(b))             */
 #define MX_OP_DIVS  7   /* C = A / s          (divide(b))               */
 #define MX_OP_RDIVS 8   /* C = s / A          (divideBy(b))             */
+/* op is one of the codes above, anything else is MX_EINVAL; ADD, SUB and
+ * EMUL read B, which must not be NULL for them. IEEE arithmetic in the
+ * element type: NaN and infinities propagate, signed zeros are kept. */
 int mx_map(mx_ctx* ctx, int op, int is_fp32, int64_t n, const void* A,
            const void* B /* null for scalar ops */, double scalar, void* C);
 int mx_sum(mx_ctx* ctx, int is_fp32, int64_t n, const void* A, double* out);
@@ -445,7 +474,11 @@ int mx_transpose(mx_ctx* ctx, int is_fp32, int64_t m, int64_t n,
 int mx_dgemv(mx_ctx* ctx, int64_t m, int64_t n, const double* A,
              const double* x, double* y);
 
-/* Device-resident gemv on a cached matrix (mx_dbuf + pitch). */
+/* Device-resident gemv on a cached matrix (mx_dbuf + pitch), fp64: y = A x
+ * with A the m x n col-major image of pitch lda in dA, x and y host
+ * vectors. m, n >= 1, lda >= m, and the (n-1) * lda + m elements of the
+ * image fit dA, else MX_EINVAL. Rows [m, lda) of the image and anything
+ * past column n are never read. */
 int mx_dgemv_device(mx_ctx* ctx, int64_t m, int64_t n, const mx_dbuf* dA,
                     int64_t lda, const double* x, double* y);
 

@@ -28,6 +28,7 @@
 #include "gemm_op_layout.h"
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
 #include "gemm_splitk_plan.h"  // the split-K slicing policy
+#include "aux_guards.h"        // argument checks of the auxiliary entries
 #include "kernels.h"           // the kernels.hip launchers
 
 #define HIP_OK(x)                                                        \
@@ -262,20 +263,21 @@ int mx_free(mx_ctx* c, mx_dbuf* b) {
   return MX_OK;
 }
 int mx_upload(mx_ctx* c, mx_dbuf* dst, const void* src, int64_t bytes) {
-  if (!c || !dst || !src || bytes > dst->bytes) return MX_EINVAL;
+  if (!c || !dst || !src || !mx_aux_bytes_ok(dst, bytes)) return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemcpy(dst->ptr, src, (size_t)bytes, hipMemcpyHostToDevice));
   return MX_OK;
 }
 int mx_download(mx_ctx* c, void* dst, const mx_dbuf* src, int64_t bytes) {
-  if (!c || !dst || !src || bytes > src->bytes) return MX_EINVAL;
+  if (!c || !dst || !src || !mx_aux_bytes_ok(src, bytes)) return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemcpy(dst, src->ptr, (size_t)bytes, hipMemcpyDeviceToHost));
   return MX_OK;
 }
 int mx_fill_random(mx_ctx* c, mx_dbuf* buf, int64_t n_elems, uint64_t seed,
                    int is_fp32) {
-  if (!c || !buf) return MX_EINVAL;
+  if (!c || !buf || !mx_aux_fill_ok(buf, is_fp32, n_elems)) return MX_EINVAL;
+  if (n_elems == 0) return MX_OK;
   HIP_OK(hipSetDevice(c->device));
   int rc = mxk_fill_random(is_fp32, buf->ptr, n_elems, 1, n_elems, seed,
                            c->s_gemm);
@@ -290,7 +292,10 @@ int mx_fill_random(mx_ctx* c, mx_dbuf* buf, int64_t n_elems, uint64_t seed,
 int mx_zero_pad(mx_ctx* c, mx_dbuf* buf, int64_t rows_total,
                 int64_t cols_total, int64_t ld, int64_t m, int64_t n,
                 int is_fp32) {
-  if (!c || !buf) return MX_EINVAL;
+  if (!c || !buf ||
+      !mx_aux_zero_pad_ok(buf, is_fp32, rows_total, cols_total, ld, m, n))
+    return MX_EINVAL;
+  if (rows_total == 0 || cols_total == 0) return MX_OK;   // empty image
   HIP_OK(hipSetDevice(c->device));
   if (mxk_zero_pad(is_fp32, buf->ptr, rows_total, cols_total, ld, m, n,
                    c->s_gemm))
@@ -317,7 +322,8 @@ int mx_download_off(mx_ctx* c, void* dst, const mx_dbuf* src,
 int mx_download2d_off(mx_ctx* c, void* dst, const mx_dbuf* src,
                       int64_t off_bytes, int64_t pitch_elems, int64_t m,
                       int64_t n, int elem) {
-  if (!c || !dst || !src || m <= 0 || n <= 0 || off_bytes < 0)
+  if (!c || !dst || !src ||
+      !mx_aux_copy2d_ok(src, elem, off_bytes, pitch_elems, m, n))
     return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemcpy2D(dst, (size_t)(m * elem),
@@ -387,8 +393,8 @@ int mx_sgemm_device(mx_ctx* c, int64_t m, int64_t k, int64_t n,
 // analog: DenseVecMatrix.cache(), DenseVecMatrix.scala:321,505 usage).
 int mx_upload2d(mx_ctx* c, mx_dbuf* dst, int64_t pitch_elems,
                 const void* src, int64_t m, int64_t n, int elem) {
-  if (!c || !dst || !src || m <= 0 || n <= 0) return MX_EINVAL;
-  if (pitch_elems * (n - 1) + m > dst->bytes / elem) return MX_EINVAL;
+  if (!c || !dst || !src || !mx_aux_copy2d_ok(dst, elem, 0, pitch_elems, m, n))
+    return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemcpy2D(dst->ptr, (size_t)(pitch_elems * elem), src,
                      (size_t)(m * elem), (size_t)(m * elem), (size_t)n,
@@ -397,7 +403,8 @@ int mx_upload2d(mx_ctx* c, mx_dbuf* dst, int64_t pitch_elems,
 }
 int mx_download2d(mx_ctx* c, void* dst, const mx_dbuf* src,
                   int64_t pitch_elems, int64_t m, int64_t n, int elem) {
-  if (!c || !dst || !src || m <= 0 || n <= 0) return MX_EINVAL;
+  if (!c || !dst || !src || !mx_aux_copy2d_ok(src, elem, 0, pitch_elems, m, n))
+    return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemcpy2D(dst, (size_t)(m * elem), src->ptr,
                      (size_t)(pitch_elems * elem), (size_t)(m * elem),
@@ -405,7 +412,7 @@ int mx_download2d(mx_ctx* c, void* dst, const mx_dbuf* src,
   return MX_OK;
 }
 int mx_memset(mx_ctx* c, mx_dbuf* b, int64_t bytes) {
-  if (!c || !b || bytes > b->bytes) return MX_EINVAL;
+  if (!c || !b || !mx_aux_bytes_ok(b, bytes)) return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipMemset(b->ptr, 0, (size_t)bytes));
   return MX_OK;
@@ -414,7 +421,9 @@ int mx_memset(mx_ctx* c, mx_dbuf* b, int64_t bytes) {
 // are zero so the transposed pads stay zero)
 int mx_transpose_device(mx_ctx* c, int is_fp32, int64_t m, int64_t n,
                         const mx_dbuf* in, mx_dbuf* out) {
-  if (!c || !in || !out) return MX_EINVAL;
+  if (!c || !in || !out || !mx_aux_transpose_ok(is_fp32, m, n, in, out))
+    return MX_EINVAL;
+  if (m == 0 || n == 0) return MX_OK;   // empty: a zero-block grid is an error
   HIP_OK(hipSetDevice(c->device));
   if (mxk_transpose(is_fp32, m, n, in->ptr, out->ptr, c->s_gemm))
     return MX_EHIP;
@@ -1156,8 +1165,8 @@ int mx_sgemm_summa(mx_ctx* c, int64_t m, int64_t k, int64_t n, const float* A,
 // elementwise ops are layout-agnostic (flat n elements).
 int mx_map(mx_ctx* c, int op, int is_fp32, int64_t n, const void* A,
            const void* B, double scalar, void* C) {
-  if (!c || !A || !C || n <= 0) return MX_EINVAL;
-  const int binary = op <= 2;
+  if (!c || !A || !C || n <= 0 || !mx_aux_map_op_ok(op)) return MX_EINVAL;
+  const int binary = mx_aux_map_binary(op);
   if (binary && !B) return MX_EINVAL;
   const int64_t elem = is_fp32 ? 4 : 8;
   HIP_OK(hipSetDevice(c->device));
@@ -1240,7 +1249,8 @@ int mx_dgemv(mx_ctx* c, int64_t m, int64_t n, const double* A,
 // matrix never crosses PCIe). lda = the DeviceMatrix pitch.
 int mx_dgemv_device(mx_ctx* c, int64_t m, int64_t n, const mx_dbuf* dA,
                     int64_t lda, const double* x, double* y) {
-  if (!c || !dA || !x || !y || m <= 0 || n <= 0) return MX_EINVAL;
+  if (!c || !dA || !x || !y || !mx_aux_gemv_ok(dA, m, n, lda))
+    return MX_EINVAL;
   HIP_OK(hipSetDevice(c->device));
   int rc;
   if ((rc = ensure(c, &c->wsB, (n + m + 32 * m) * 8))) return rc;

@@ -7,6 +7,7 @@
 import numpy as np
 import pytest
 
+from _linalg_cases import lu_residual, shuffled_dominant
 from marlin_amd import Engine, DenseVecMatrix
 from oracle import gen_matrix
 
@@ -64,6 +65,25 @@ def test_lu_grouped_bits_equal_loop(eng, n, base):
     np.testing.assert_array_equal(p1, p0)
     L = np.tril(lu1, -1) + np.eye(n)
     rel = np.max(np.abs(a[p1, :] - L @ np.triu(lu1))) / np.max(np.abs(a))
+    assert rel < 1e-10, rel
+
+
+@pytest.mark.parametrize("n,base", [(300, 96), (64, 16)])
+def test_lu_pivoting_grouped_bits_equal_loop(eng, n, base):
+    # an input on which p_array is not the identity (rows shuffled inside
+    # each block row): L^-1 P feeds the batches of both arms
+    a, src = shuffled_dominant(n, base)
+
+    def run(g):
+        blk, p = DenseVecMatrix(a, engine=eng).luDecompose(
+            mode="dist", base_size=base, grouped=g)
+        return blk.toBreeze(), p
+    (lu0, p0), (lu1, p1) = _both(eng, run)
+    _bits_equal(lu1, lu0)
+    np.testing.assert_array_equal(p1, p0)
+    assert (p1 != np.arange(n)).any()
+    np.testing.assert_array_equal(src[p1], np.arange(n))
+    rel = lu_residual(a, lu1, p1)
     assert rel < 1e-10, rel
 
 

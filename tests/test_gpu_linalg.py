@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+from _linalg_cases import lu_residual, shuffled_dominant
 from marlin_amd import Engine, DenseVecMatrix
 from oracle import gen_matrix
 
@@ -49,6 +50,19 @@ def test_lu_dist_route(eng, n, base):
     # block pairwise pivoting property: P_blockdiag A == L U
     PA = a[p_array, :]
     rel = np.max(np.abs(PA - L @ U)) / np.max(np.abs(a))
+    assert rel < 1e-10, rel
+
+
+@pytest.mark.parametrize("n,base", [(300, 96), (64, 16)])
+def test_lu_dist_route_pivots(eng, n, base):
+    # rows shuffled inside each block row: the perm loop, L^-1 P in the
+    # panel factor and the sub-diagonal fix-up all have work to do
+    a, src = shuffled_dominant(n, base)
+    blk, p_array = DenseVecMatrix(a, engine=eng).luDecompose(
+        mode="dist", base_size=base)
+    assert (p_array != np.arange(n)).any()
+    np.testing.assert_array_equal(src[p_array], np.arange(n))
+    rel = lu_residual(a, blk.toBreeze(), p_array)
     assert rel < 1e-10, rel
 
 
