@@ -349,6 +349,65 @@ int mx_gemm_device_splitk(mx_ctx* ctx, int is_fp32, int beta_one, int trans_a,
  * this process: (1, 0) after an unsplit one, (0, 0) before the first. */
 int mx_last_gemm_splitk(mx_ctx* ctx, int* slices, int64_t* workspace_bytes);
 
+/* Triangular solve (BLAS TRSM with alpha = 1) on device images, fp64
+ * (is_fp32 = 0) or fp32:
+ *     side = 0:  op(T) * X = B,  B stored n x r   (r right-hand-side columns)
+ *     side = 1:  X * op(T) = B,  B stored r x n   (r right-hand-side rows)
+ * op(T) = T or T^T per trans, T triangular of order n, lower or upper per
+ * lower, with an implied unit diagonal when unit_diag. X overwrites B. T is
+ * read AS STORED: no transposed copy is made. All 16 forms exist in both
+ * element types; every flag, is_fp32 included, is 0 or 1.
+ *
+ * Sizes and pitches. n is the logical order; np = n rounded up to 128.
+ * r is a multiple of 128. The T image is np x np at pitch ldt >= np. The B
+ * image is np x r with ldb >= np (left) or r x np with ldb >= r (right).
+ * Both pitches are multiples of 16 bytes.
+ *
+ * What is read. Of T only the referenced triangle: the opposite triangle is
+ * never read, and with unit_diag neither is the diagonal, so a packed L\U
+ * factor serves as L (lower, unit) and as U (upper) from one buffer. Inside
+ * the last diagonal block nothing at a row or column index >= n is read:
+ * the block is continued as the identity. The off-diagonal 128 x 128 blocks
+ * of the referenced triangle are read whole by a GEMM, so their part at an
+ * index >= n must be zero (what a zero-initialised padded image holds).
+ *
+ * What is written. The pad rows (left) or columns (right) [n, np) of B must
+ * be zero on entry and are zero on exit. Rows of B past np (left) or past r
+ * (right), up to the pitch, are neither read nor written, nor is anything
+ * past the last column of the image.
+ *
+ * Checks. Everything is checked before anything is enqueued or allocated
+ * (marlin_amd/csrc/trsm_plan.h is the code): the flags, n and r >= 0 and r a
+ * multiple of 128, NULL handles, the pitches, both images against the sizes
+ * their buffers were allocated with (overflow-safely), and aliasing: dT and
+ * dB must be different handles whose device ranges share no byte. A refused
+ * call returns MX_EINVAL and has touched no buffer. n == 0 or r == 0 is a
+ * no-op that returns MX_OK and looks at neither buffer. A zero on the
+ * diagonal gives inf / NaN as in BLAS; no singularity check is made.
+ *
+ * Algorithm, fixed so that the result does not depend on the schedule or
+ * the run. Blocks are 128 wide; with eff_lower = lower XOR trans the left
+ * side sweeps the blocks forward when eff_lower and the right side when
+ * !eff_lower, otherwise backward. Step j (a) solves diagonal block j against
+ * all r right-hand sides with the diagonal kernel, substitution in
+ * ascending order of the eliminated index, which writes X_j into B and -X_j
+ * into a workspace panel of 128 * r elements the context owns (grown on
+ * demand, freed by mx_shutdown), then (b) accumulates into ALL remaining
+ * blocks with one launch of the plain GEMM (beta_one = 1, k = 128):
+ *     left:   B_rest += op(T)[rest, j] * (-X_j)
+ *     right:  B_rest += (-X_j) * op(T)[j, rest]
+ * with op(T)'s block passed as stored under the GEMM's trans_a / trans_b.
+ * No atomics; the GEMM is an existing instantiation of the closed list.
+ *
+ * Stats: flops = n * n * r, gemm_launches = the update GEMMs launched
+ * (np / 128 - 1), gemm_ms = event time over the whole sweep, diagonal
+ * kernels included; the other fields are zero. mx_last_gemm_config, _op and
+ * _loop report the last update GEMM of the sweep (unchanged when n <= 128,
+ * which has none). */
+int mx_trsm_device(mx_ctx* ctx, int is_fp32, int side, int lower, int trans,
+                   int unit_diag, int64_t n, int64_t r,
+                   const mx_dbuf* dT, int64_t ldt, mx_dbuf* dB, int64_t ldb);
+
 /* Introspection: the gemm_mfma_kernel instantiation and remap arguments
  * of the most recent plain GEMM launch in this process (any entry that
  * reaches the kernel launcher; all zero before the first launch). The
@@ -465,6 +524,13 @@ int mx_test_rccl_error(mx_ctx* ctx);
  * element type: NaN and infinities propagate, signed zeros are kept. */
 int mx_map(mx_ctx* ctx, int op, int is_fp32, int64_t n, const void* A,
            const void* B /* null for scalar ops */, double scalar, void* C);
+/* mx_map on device buffers, nothing crosses PCIe: the first n elements of
+ * dA (and of dB for ADD, SUB, EMUL; NULL otherwise) into the first n of dC.
+ * n >= 0 and n elements fit every buffer named, is_fp32 in {0,1}, op as
+ * above, else MX_EINVAL; n == 0 is a no-op. dC may be dA or dB (in place). */
+int mx_map_device(mx_ctx* ctx, int op, int is_fp32, int64_t n,
+                  const mx_dbuf* dA, const mx_dbuf* dB, double scalar,
+                  mx_dbuf* dC);
 int mx_sum(mx_ctx* ctx, int is_fp32, int64_t n, const void* A, double* out);
 int mx_transpose(mx_ctx* ctx, int is_fp32, int64_t m, int64_t n,
                  const void* A, void* C /* n x m col-major */);

@@ -302,11 +302,25 @@ class DenseVecMatrix:
             d.free()
         return out
 
-    def choleskyDecompose(self, mode="auto", base_size=1000, grouped=True):
+    def choleskyDecompose(self, mode="auto", base_size=1000, grouped=True,
+                          panel="inverse"):
         """DenseVecMatrix.choleskyDecompose (DenseVecMatrix.scala:475-566).
-        grouped=False keeps one launch per block product (same bits)."""
+        grouped=False keeps one launch per block product (same bits).
+        panel="trsm" gets each column panel from one device triangular
+        solve instead of a product with the host inverse of L11."""
         from .linalg import cholesky_decompose
-        return cholesky_decompose(self, mode, base_size, grouped)
+        return cholesky_decompose(self, mode, base_size, grouped, panel)
+
+    def solve(self, rhs, mode="auto", base_size=1000):
+        """x with A x = rhs (a vector, or a matrix of right-hand-side
+        columns): luDecompose(mode, base_size), then two triangular solves
+        on the device against the packed factor (linalg.lu_solve). No
+        inverse is formed."""
+        from .linalg import lu_decompose, lu_solve
+        blocks, p_array = lu_decompose(self, mode, base_size)
+        if blocks._eng is None:
+            blocks._eng = self._engine()
+        return lu_solve(blocks, p_array, rhs)
 
     def toBreeze(self):
         return self._host().copy()

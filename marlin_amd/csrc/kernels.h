@@ -46,6 +46,12 @@ int mxk_gemm_grouped(int is_fp32, int beta_one, int trans_a, int trans_b,
 // element type; slab j is the tight m x n image at W + j * m * n.
 int mxk_splitk_reduce(int is_fp32, int64_t m, int64_t n, void* C, int64_t ldc,
                       const void* W, int nslabs, hipStream_t stream);
+// One 128 x 128 diagonal block of mx_trsm_device against r right-hand
+// sides: X overwrites its strip of B, -X fills the workspace panel ws
+// (128 * r elements). tt, rev, unit, nv as mx_trsm_stage (trsm_plan.h).
+int mxk_trsm_diag(int is_fp32, int side, int tt, int rev, int unit, int nv,
+                  const void* Tjj, int64_t ldt, void* X, int64_t ldx,
+                  void* ws, int64_t r, hipStream_t stream);
 int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K, const float* A,
                           int64_t lda, const float* B, int64_t ldb, float* C,
                           int64_t ldc, const float* addC, hipStream_t stream);

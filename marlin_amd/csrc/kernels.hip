@@ -648,10 +648,12 @@ __global__ void zero_pad_kernel(T* __restrict__ buf, int64_t rows_total,
 // Op codes: MX_OP_* of include/marlin_gpu.h (ADD/SUB/EMUL binary, then
 // ADDS, SUBS, RSUBS = s - A, MULS, DIVS, RDIVS = s / A).
 
+// c may be a or b (mx_map and mx_map_device both run it in place): element
+// i is read before it is written and no other is touched, so the pointers
+// are not declared __restrict__.
 template <typename T>
-__global__ void map_kernel(int op, int64_t n, const T* __restrict__ a,
-                           const T* __restrict__ b, double scalar,
-                           T* __restrict__ c) {
+__global__ void map_kernel(int op, int64_t n, const T* a, const T* b,
+                           double scalar, T* c) {
     const T s = (T)scalar;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -832,6 +834,169 @@ splitk_reduce_kernel(T* __restrict__ C, int64_t ldc, int64_t m, int64_t n,
 }
 
 // ---------------------------------------------------------------------------
+// Triangular solve, the diagonal blocks (mx_trsm_device; the sweep around
+// them is trsm_plan.h). One launch solves ONE 128 x 128 diagonal block of T
+// against all r right-hand sides: X_j overwrites its strip of B and -X_j
+// goes to the workspace panel, which the accumulating GEMM of the step then
+// multiplies into every remaining block. It carries 128 / n of the flops
+// and is one-shot and latency-bound, so it is built for fixed arithmetic
+// and coalesced traffic, not for peak rate.
+//
+//   - One right-hand side per lane, 64 per block (one wave), r / 64 blocks.
+//     Every lane runs the same forward substitution on a lower-triangular
+//     L, y_a = (v_a - sum_{b<a} L[a][b] y_b) / L[a][a], subtracting in
+//     ascending b: the order of a result's operations is fixed by the code
+//     alone, no atomics, no cross-lane sums. Side, triangle, transpose and
+//     unit diagonal are resolved when L is staged (mx_trsm_stage: transpose
+//     on load, reversal of the index for an upper form, 1 on a unit
+//     diagonal, the identity at an index >= nv), element by element, so
+//     only the referenced triangle below the order of T is ever loaded.
+//   - The strip of B lives in LDS as tile[a][lane] (pitch 65: the strip
+//     loads and stores walk it along a, the substitution along the lanes,
+//     neither with more than a 2-way bank conflict). It moves to and from
+//     global memory in 16-byte chunks along whichever dimension is
+//     contiguous there: the rows of the strip on the left side (a lane per
+//     column would stride by the pitch), the right-hand sides on the right.
+//   - L is staged 32 rows at a time as Lp[b][i], 32 KB in fp64, which with
+//     the 65 KB tile fits the 160 KB of LDS where the whole block (128 KB)
+//     would not. A lane keeps the 32 rows of its vector it is solving in
+//     registers (64 VGPRs in fp64), never all 128; finished rows are read
+//     back from the tile, L from Lp at a wave-uniform address (a broadcast).
+#define TRSM_FN __host__ __device__ __forceinline__
+#include "trsm_plan.h"
+
+constexpr int TRSM_W = 128;              // order of a diagonal block
+constexpr int TRSM_RB = 64;              // right-hand sides per block
+constexpr int TRSM_PB = 32;              // rows of L staged at a time
+constexpr int TRSM_TP = TRSM_RB + 1;     // pitch of the LDS tile
+
+// The 128 x 64 strip between global memory and the tile. g is its first
+// element: on the left side 128 contiguous rows by 64 columns of pitch
+// `pitch`, on the right 64 contiguous right-hand sides by 128 columns.
+template <typename T, int SIDE, int STORE>
+DEVFN void trsm_strip_io(T* __restrict__ g, int64_t pitch, T* tile, int rev,
+                         int lane, T sign) {
+    using V = typename chunk16_t<T>::type;
+    constexpr int E = 16 / sizeof(T);
+    constexpr int D = SIDE ? TRSM_RB : TRSM_W;     // the contiguous extent
+    constexpr int O = SIDE ? TRSM_W : TRSM_RB;     // the pitched one
+    constexpr int STEP = 64 * E / D;               // columns per instruction
+    const int u = (lane * E) % D, dv = (lane * E) / D;
+    #pragma unroll 8
+    for (int v = 0; v < O; v += STEP) {
+        V* p = reinterpret_cast<V*>(g + u + (int64_t)(v + dv) * pitch);
+        V x;
+        if (!STORE) x = *p;
+        #pragma unroll
+        for (int e = 0; e < E; e++) {
+            const int o = SIDE ? v + dv : u + e;   // index inside the block
+            const int c = SIDE ? u + e : v + dv;   // right-hand side
+            T* t = &tile[mx_trsm_orig(TRSM_W, rev, o) * TRSM_TP + c];
+            if (STORE) x[e] = sign * *t; else *t = x[e];
+        }
+        if (STORE) *p = x;
+    }
+}
+
+// One element of L as mx_trsm_stage defines it. The load is unconditional,
+// so that an unrolled staging loop has all its loads in flight at once
+// instead of one round trip per element: a lane with nothing to load reads
+// this idle word instead, never an element of T outside the referenced
+// triangle.
+__device__ double mx_trsm_idle[2] = {0.0, 0.0};
+
+template <typename T>
+DEVFN T trsm_stage_elem(const T* __restrict__ Tjj, int64_t ldt, int tt,
+                        int rev, int unit, int nv, int a, int b) {
+    int64_t off = 0;
+    const int kind = mx_trsm_stage(TRSM_W, tt, rev, unit, nv, a, b, ldt, &off);
+    const T* src = kind == MX_TRSM_LOAD
+                       ? Tjj + off
+                       : reinterpret_cast<const T*>(mx_trsm_idle);
+    const T v = *src;
+    return kind == MX_TRSM_LOAD ? v : T(kind);
+}
+
+template <typename T, int SIDE>
+__global__ void __launch_bounds__(TRSM_RB)
+trsm_diag_kernel(const T* __restrict__ Tjj, int64_t ldt, T* __restrict__ X,
+                 int64_t ldx, T* __restrict__ ws, int64_t ldw, int tt,
+                 int rev, int unit, int nv) {
+    __shared__ __attribute__((aligned(16)))
+        T smem[TRSM_W * TRSM_PB + TRSM_W * TRSM_TP];
+    T* Lp = smem;                        // Lp[b * 32 + i] = L[32 s + i][b]
+    T* tile = smem + TRSM_W * TRSM_PB;   // tile[a * 65 + lane]
+    const int lane = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * TRSM_RB;
+    T* xg = X + (SIDE ? c0 : c0 * ldx);
+    T* wg = ws + (SIDE ? c0 : c0 * ldw);
+    trsm_strip_io<T, SIDE, 0>(xg, ldx, tile, rev, lane, T(1));
+
+    #pragma unroll 1
+    for (int s = 0; s < TRSM_W / TRSM_PB; s++) {
+        const int a0 = s * TRSM_PB, cols = a0 + TRSM_PB;
+        __syncthreads();                 // the previous panel is done with
+        // stage rows [a0, a0 + 32) of L, columns [0, a0 + 32); the lanes
+        // run along whichever index is contiguous in T as stored, eight
+        // loads per lane in flight before the first is stored
+        if (!tt) {
+            const int i = lane & 31;
+            for (int b0 = lane >> 5; b0 < cols; b0 += 16) {
+                T v[8];
+                #pragma unroll
+                for (int q = 0; q < 8; q++)
+                    v[q] = trsm_stage_elem(Tjj, ldt, tt, rev, unit, nv, a0 + i,
+                                           b0 + 2 * q);
+                #pragma unroll
+                for (int q = 0; q < 8; q++)
+                    Lp[(b0 + 2 * q) * TRSM_PB + i] = v[q];
+            }
+        } else {
+            // columns [cols, 128) of Lp are written too (zeros: a < b
+            // there); no later read of this panel looks at them
+            for (int i0 = 0; i0 < TRSM_PB; i0 += 4) {
+                T v[8];
+                #pragma unroll
+                for (int q = 0; q < 8; q++)
+                    v[q] = trsm_stage_elem(Tjj, ldt, tt, rev, unit, nv,
+                                           a0 + i0 + (q >> 1),
+                                           lane + 64 * (q & 1));
+                #pragma unroll
+                for (int q = 0; q < 8; q++)
+                    Lp[(lane + 64 * (q & 1)) * TRSM_PB + i0 + (q >> 1)] = v[q];
+            }
+        }
+        __syncthreads();
+
+        T y[TRSM_PB];
+        #pragma unroll
+        for (int i = 0; i < TRSM_PB; i++)
+            y[i] = tile[(a0 + i) * TRSM_TP + lane];
+        // the rows solved by earlier panels
+        for (int b = 0; b < a0; b++) {
+            const T yb = tile[b * TRSM_TP + lane];
+            const T* col = Lp + b * TRSM_PB;
+            #pragma unroll
+            for (int i = 0; i < TRSM_PB; i++) y[i] -= col[i] * yb;
+        }
+        // the triangle of this panel, in registers
+        #pragma unroll
+        for (int i = 0; i < TRSM_PB; i++) {
+            const T* col = Lp + (a0 + i) * TRSM_PB;
+            y[i] = y[i] / col[i];
+            #pragma unroll
+            for (int i2 = i + 1; i2 < TRSM_PB; i2++) y[i2] -= col[i2] * y[i];
+        }
+        #pragma unroll
+        for (int i = 0; i < TRSM_PB; i++)
+            tile[(a0 + i) * TRSM_TP + lane] = y[i];
+    }
+    __syncthreads();
+    trsm_strip_io<T, SIDE, 1>(xg, ldx, tile, rev, lane, T(1));
+    trsm_strip_io<T, SIDE, 1>(wg, ldw, tile, rev, lane, T(-1));
+}
+
+// ---------------------------------------------------------------------------
 // GEMM launch. Which instantiation a call runs is decided in
 // gemm_launch_policy.h; here are the latched knobs, the record of the last
 // launch, the one step from a selected variant to its compiled kernel, and
@@ -926,6 +1091,38 @@ int mxk_splitk_reduce(int is_fp32, int64_t m, int64_t n, void* C, int64_t ldc,
         hipLaunchKernelGGL(splitk_reduce_kernel<double>, grid, block, 0,
                            stream, (double*)C, ldc, m, n, (const double*)W,
                            m * n, nslabs);
+    return (int)hipGetLastError() == 0 ? 0 : -2;
+}
+
+// One diagonal block of the triangular solve. Tjj is the block's first
+// element in T (pitch ldt), X the first element of its strip of B (left:
+// 128 rows x r columns, right: r rows x 128 columns, pitch ldx), ws the
+// panel that receives -X (left: 128 x r at pitch 128, right: r x 128 at
+// pitch r). tt, rev, unit, nv: mx_trsm_stage. r is a positive multiple of
+// 128, so the r / 64 blocks cover it exactly and no lane is out of range.
+int mxk_trsm_diag(int is_fp32, int side, int tt, int rev, int unit, int nv,
+                  const void* Tjj, int64_t ldt, void* X, int64_t ldx,
+                  void* ws, int64_t r, hipStream_t stream) {
+    const int64_t e16 = is_fp32 ? 4 : 2;
+    if ((is_fp32 | side | tt | rev | unit) & ~1) return -4;
+    if (nv < 1 || nv > TRSM_W || r <= 0 || r % 128) return -4;
+    if (r / TRSM_RB > INT32_MAX || !Tjj || !X || !ws) return -4;
+    if (!pitch_ok(ldt, TRSM_W, e16) || !pitch_ok(ldx, side ? r : TRSM_W, e16))
+        return -4;
+    const dim3 grid((unsigned)(r / TRSM_RB)), block(TRSM_RB);
+    const int64_t ldw = side ? r : TRSM_W;
+    auto launch = [&](auto t, auto kernel) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, (const T*)Tjj, ldt,
+                           (T*)X, ldx, (T*)ws, ldw, tt, rev, unit, nv);
+    };
+    if (is_fp32) {
+        if (side) launch(float{}, trsm_diag_kernel<float, 1>);
+        else launch(float{}, trsm_diag_kernel<float, 0>);
+    } else {
+        if (side) launch(double{}, trsm_diag_kernel<double, 1>);
+        else launch(double{}, trsm_diag_kernel<double, 0>);
+    }
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 

@@ -28,6 +28,7 @@
 #include "gemm_op_layout.h"
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
 #include "gemm_splitk_plan.h"  // the split-K slicing policy
+#include "trsm_plan.h"         // the triangular solve: check and step list
 #include "aux_guards.h"        // argument checks of the auxiliary entries
 #include "kernels.h"           // the kernels.hip launchers
 
@@ -100,6 +101,9 @@ struct mx_ctx {
   std::vector<mx_splitk_slice> splitk_slices;
   std::vector<mx_gemm_problem_t> splitk_rows;
   int cus = 0;
+  // triangular solve: the -X_j panel (128 * r elements) and the step list
+  mx_dbuf wsT;
+  mx_trsm_plan trsm_plan;
   mx_stats_t st = {};
 };
 
@@ -167,7 +171,7 @@ int mx_shutdown(mx_ctx* c) {
   if (c->world) ncclCommDestroy(c->world);
   for (mx_dbuf* b : {&c->wsA, &c->wsB, &c->wsC,
                      &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1],
-                     &c->wsG, &c->wsK})
+                     &c->wsG, &c->wsK, &c->wsT})
     if (b->ptr) (void)hipFree(b->ptr);
   ctx_teardown(c);
   return MX_OK;
@@ -566,6 +570,52 @@ int mx_gemm_device_splitk(mx_ctx* c, int is_fp32, int beta_one, int trans_a,
   });
   if (rc == MX_OK) mxk_note_splitk(S, ws_bytes);   // only a split that ran
   return rc;
+}
+
+// Triangular solve on device images (include/marlin_gpu.h). The check and
+// the step list are trsm_plan.h; only a call that passed the whole check
+// allocates or enqueues. Every step is the diagonal kernel, then one
+// accumulating GEMM into all remaining blocks, in stream order on s_gemm.
+int mx_trsm_device(mx_ctx* c, int is_fp32, int side, int lower, int trans,
+                   int unit_diag, int64_t n, int64_t r, const mx_dbuf* dT,
+                   int64_t ldt, mx_dbuf* dB, int64_t ldb) {
+  if (!c) return MX_EINVAL;
+  c->st = {};
+  bool empty = false;
+  int rc = mx_trsm_check(128, is_fp32, side, lower, trans, unit_diag, n, r, dT,
+                         ldt, dB, ldb, &empty);
+  if (rc) return rc;
+  c->st.flops = (double)n * (double)n * (double)r;
+  if (empty) return MX_OK;
+  mx_trsm_plan& plan = c->trsm_plan;
+  mx_trsm_steps(128, side, lower, trans, n, r, ldt, ldb, &plan);
+  const int64_t elem = is_fp32 ? 4 : 8;
+  HIP_OK(hipSetDevice(c->device));
+  if (plan.ws_elems > INT64_MAX / elem) return MX_ENOMEM;
+  if ((rc = ensure(c, &c->wsT, plan.ws_elems * elem))) return rc;
+  const char* tp = (const char*)dT->ptr;
+  char* bp = (char*)dB->ptr;
+  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
+  for (const mx_trsm_step& st : plan.steps) {
+    rc = mxk_trsm_diag(is_fp32, side, plan.tt, plan.rev, unit_diag, st.nv,
+                       tp + st.t_off * elem, ldt, bp + st.x_off * elem, ldb,
+                       c->wsT.ptr, r, c->s_gemm);
+    if (rc) return launch_status(rc);
+    if (st.rest_len == 0) continue;
+    const void* A = side ? c->wsT.ptr : (const void*)(tp + st.a_off * elem);
+    const void* B = side ? (const void*)(tp + st.b_off * elem) : c->wsT.ptr;
+    rc = mxk_gemm_op(is_fp32, 1, st.trans_a, st.trans_b, st.gm, st.gn, st.gk,
+                     A, st.lda, B, st.ldb, bp + st.c_off * elem, st.ldc,
+                     c->s_gemm);
+    if (rc) return launch_status(rc);
+    c->st.gemm_launches += 1;
+  }
+  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
+  HIP_OK(hipEventSynchronize(c->ev[1]));
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  c->st.gemm_ms = ms;
+  return MX_OK;
 }
 
 // The mx_last_gemm_* entries: views of the one record kernels.hip keeps.
@@ -1183,6 +1233,25 @@ int mx_map(mx_ctx* c, int op, int is_fp32, int64_t n, const void* A,
     return MX_EHIP;
   HIP_OK(hipMemcpyAsync(C, c->wsA.ptr, n * elem, hipMemcpyDeviceToHost,
                         c->s_gemm));
+  HIP_OK(hipStreamSynchronize(c->s_gemm));
+  return MX_OK;
+}
+
+// mx_map on device buffers: the same kernel, nothing crosses PCIe.
+int mx_map_device(mx_ctx* c, int op, int is_fp32, int64_t n, const mx_dbuf* dA,
+                  const mx_dbuf* dB, double scalar, mx_dbuf* dC) {
+  if (!c || !dA || !dC || (is_fp32 & ~1) || !mx_aux_map_op_ok(op))
+    return MX_EINVAL;
+  const int binary = mx_aux_map_binary(op);
+  if (binary && !dB) return MX_EINVAL;
+  if (!mx_aux_fill_ok(dA, is_fp32, n) || !mx_aux_fill_ok(dC, is_fp32, n) ||
+      (binary && !mx_aux_fill_ok(dB, is_fp32, n)))
+    return MX_EINVAL;
+  if (n == 0) return MX_OK;
+  HIP_OK(hipSetDevice(c->device));
+  if (mxk_map(is_fp32, op, n, dA->ptr, binary ? dB->ptr : nullptr, scalar,
+              dC->ptr, c->s_gemm))
+    return MX_EHIP;
   HIP_OK(hipStreamSynchronize(c->s_gemm));
   return MX_OK;
 }

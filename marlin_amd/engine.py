@@ -159,6 +159,10 @@ def _load():
                                   + [i64, i64, i64, vp, i64, vp, i64, vp, i64,
                                      ctypes.c_int]),
         "mx_last_gemm_splitk": (ctypes.c_int, [vp, P(ctypes.c_int), P(i64)]),
+        "mx_trsm_device": (ctypes.c_int, [vp] + [ctypes.c_int] * 5
+                           + [i64, i64, vp, i64, vp, i64]),
+        "mx_map_device": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, i64,
+                                         vp, vp, dbl, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -704,6 +708,54 @@ class Engine:
                                       ctypes.byref(ws)),
             "mx_last_gemm_splitk")
         return s.value, ws.value
+
+    _SIDES = {"left": 0, "right": 1, 0: 0, 1: 1}
+
+    def trsm_raw(self, n, r, dT, ldt, dB, ldb, side=0, lower=1, trans=0,
+                 unit_diag=0, fp32=False, check=True):
+        """mx_trsm_device on raw device buffers: op(T) X = B (side 0, B is
+        n x r) or X op(T) = B (side 1, B is r x n), X over B. n is the
+        logical order, r a multiple of 128, pitches in elements. Returns
+        the entry's code; check=True raises on a non-zero one."""
+        rc = lib().mx_trsm_device(self._ctx, int(fp32), int(side), int(lower),
+                                  int(trans), int(unit_diag), n, r, dT, ldt,
+                                  dB, ldb)
+        if check:
+            _ck(rc, "mx_trsm_device")
+        return rc
+
+    def trsm_dd(self, T, B, side="left", lower=True, trans=False,
+                unit_diag=False):
+        """Triangular solve on cached matrices, in place: B becomes X with
+        op(T) @ X = B (side="left") or X @ op(T) = B ("right"). T is the
+        square triangular DeviceMatrix, read as stored and only in the
+        triangle named (a packed L\\U image serves as both factors). The
+        zero pads of the two images are what the padded solve needs, and
+        B's stay zero. Returns B."""
+        assert T.fp32 == B.fp32
+        s = self._SIDES[side]
+        n = T.m
+        if T.n != n:
+            raise ValueError(f"triangular matrix must be square: {T.m} x {T.n}")
+        if (B.n if s else B.m) != n:
+            raise ValueError(f"{_MISMATCH}: {n} vs {B.n if s else B.m}")
+        # right-hand sides: B's columns up to its column capacity on the
+        # left, its rows up to the pitch on the right
+        r = B.pitch if s else (B.n + 127) // 128 * 128
+        self.trsm_raw(n, r, T.buf, T.pitch, B.buf, B.pitch, s, lower, trans,
+                      unit_diag, T.fp32)
+        return B
+
+    def map_raw(self, op, n, dA, dB, scalar, dC, fp32=False, check=True):
+        """mx_map_device on raw device buffers: the elementwise op (a name
+        of OPS) over the first n elements of dA (and dB for the binary
+        ops, else None) into dC, which may be dA. Returns the entry's
+        code; check=True raises on a non-zero one."""
+        rc = lib().mx_map_device(self._ctx, self.OPS[op], 1 if fp32 else 0,
+                                 n, dA, dB, float(scalar), dC)
+        if check:
+            _ck(rc, "mx_map_device")
+        return rc
 
     def gemm_grouped_raw(self, problems, fp32=False, accumulate=False,
                          trans_a=False, trans_b=False, check=True):

@@ -10,7 +10,9 @@
 # All blocks stay DEVICE-RESIDENT (DeviceMatrix) across the sweeps —
 # the RDD.cache() analog — so only the base-sized diagonal factors cross
 # PCIe; sign flips are folded into the small host factors so no device
-# elementwise pass is needed.
+# elementwise pass is needed. cholesky_decompose(panel="trsm") and lu_solve
+# instead use the device triangular solve (Engine.trsm_raw / trsm_dd): no
+# inverse is formed and the factor is uploaded once.
 #
 # luDecompose: block pairwise pivoting (pivoting INSIDE each diagonal
 # block only — the reference's scheme). Returns (blocks, p_array) with
@@ -209,14 +211,136 @@ def inverse(dvm, mode="auto", base_size=1000, grouped=True):
     return BlockMatrix(out, n, n, engine=dvm._eng)
 
 
-def cholesky_decompose(dvm, mode="auto", base_size=1000, grouped=True):
+def lu_solve(lu_blocks, p_array, rhs):
+    """x with A x = rhs from the factors lu_decompose returned for A: the
+    packed L\\U blocks and p_array, for which A[p_array, :] == L @ U, so
+    that L U x = rhs[p_array]. The right-hand side is permuted on the host,
+    the packed factor is uploaded ONCE and read twice as stored by the
+    device triangular solve (Engine.trsm_dd): as unit-lower L, then as
+    upper U. rhs is a vector of n or an n x c matrix (its columns are
+    padded to 128 on the device); the result has its shape."""
+    eng = lu_blocks._engine()
+    lu = lu_blocks.toBreeze()
+    n = lu.shape[0]
+    b = np.asarray(rhs, dtype=np.float64)
+    if b.ndim not in (1, 2) or b.shape[0] != n:
+        raise ValueError(f"right-hand side must have {n} rows: {b.shape}")
+    pb = b.reshape(n, -1)[np.asarray(p_array), :]   # (P b)[g] = b[p_array[g]]
+    d_lu = eng.upload_matrix(lu)
+    d_b = eng.upload_matrix(pb)
+    try:
+        eng.trsm_dd(d_lu, d_b, side="left", lower=True, unit_diag=True)
+        eng.trsm_dd(d_lu, d_b, side="left", lower=False)
+        x = eng.download_matrix(d_b)
+    finally:
+        d_lu.free()
+        d_b.free()
+    return x[:, 0] if b.ndim == 1 else x
+
+
+def _r128(x):
+    return (x + 127) // 128 * 128
+
+
+def _cholesky_trsm(eng, a, nb, offs, lens):
+    """The blocked sweep of cholesky_decompose(panel="trsm"). Block column
+    j lives on the device as its diagonal block (a DeviceMatrix) and ONE
+    panel image holding the blocks (j+1.., j) stacked, each padded to 128
+    rows, so that the whole column panel is the B of a single right-side
+    solve, L21 = A21 L11^-T, against the once-uploaded L11; its negated
+    copy for the trailing update is an elementwise pass on the device, and
+    the update's products address their blocks by offset into the panels.
+    Returns the host blocks of the lower triangle."""
+    rp = [_r128(ln) for ln in lens]
+    top = [sum(rp[:i]) for i in range(nb + 1)]      # padded row of block i
+    diag, panel, rows = {}, {}, {}
+    # one host staging area for every panel image, up and down: a fresh
+    # array per panel would be page-faulted in anew each time
+    stage = np.zeros((top[nb] - top[1]) * max(rp))
+
+    def image(j):
+        return stage[:rows[j] * rp[j]].reshape((rows[j], rp[j]), order="F")
+    for j in range(nb):
+        diag[j] = eng.upload_matrix(a[offs[j]:offs[j] + lens[j],
+                                      offs[j]:offs[j] + lens[j]])
+        rows[j] = top[nb] - top[j + 1]              # pitch of panel j
+        if rows[j] == 0:
+            continue
+        img = image(j)
+        img[:, lens[j]:] = 0                        # the pads only
+        for r in range(j + 1, nb):
+            o = top[r] - top[j + 1]
+            img[o + lens[r]:o + rp[r], :] = 0
+            # block by block into column-major first: one strided pass over
+            # a whole row-major column panel is several times slower
+            img[o:o + lens[r], :lens[j]] = np.asfortranarray(
+                a[offs[r]:offs[r] + lens[r], offs[j]:offs[j] + lens[j]])
+        panel[j] = eng.alloc(img.nbytes)
+        eng.upload(panel[j], img, img.nbytes)
+    host = {}
+    try:
+        for i in range(nb):
+            d = eng.download_matrix(diag[i])
+            d = np.tril(d) + np.tril(d, -1).T       # symmetrize (ref does)
+            L11 = np.linalg.cholesky(d)
+            host[(i, i)] = L11
+            if i == nb - 1:
+                break
+            d_L = neg = None
+            try:
+                d_L = eng.upload_matrix(L11)
+                neg = eng.alloc(rows[i] * rp[i] * 8)
+                # X L11^T = A21 over the whole panel: right, lower, trans
+                eng.trsm_raw(lens[i], rows[i], d_L.buf, d_L.pitch, panel[i],
+                             rows[i], side=1, lower=1, trans=1, unit_diag=0)
+                eng.map_raw("muls", rows[i] * rp[i], panel[i], None, -1.0, neg)
+                # A22[r, c] += L21[r] @ (-L21[c])^T, c <= r, as stored
+                kp = (lens[i] + 15) // 16 * 16
+                prods = []
+                for c in range(i + 1, nb):
+                    for r in range(c, nb):
+                        cbuf, coff, ldc = ((diag[c].buf, 0, diag[c].pitch)
+                                           if r == c else
+                                           (panel[c], top[r] - top[c + 1],
+                                            rows[c]))
+                        prods.append((rp[r], kp, rp[c],
+                                      panel[i], top[r] - top[i + 1], rows[i],
+                                      neg, top[c] - top[i + 1], rows[i],
+                                      cbuf, coff, ldc))
+                eng.gemm_grouped_raw(prods, accumulate=True, trans_b=True)
+            finally:
+                if d_L is not None:
+                    d_L.free()
+                if neg is not None:
+                    eng.free(neg)
+        for j, buf in panel.items():
+            img = image(j)
+            eng.download(img, buf, img.nbytes)
+            for r in range(j + 1, nb):
+                o = top[r] - top[j + 1]
+                host[(r, j)] = img[o:o + lens[r], :lens[j]].copy(order="F")
+    finally:
+        for d in diag.values():
+            d.free()
+        for buf in panel.values():
+            eng.free(buf)
+    return host
+
+
+def cholesky_decompose(dvm, mode="auto", base_size=1000, grouped=True,
+                       panel="inverse"):
     """DenseVecMatrix.choleskyDecompose (DenseVecMatrix.scala:475-566):
     A = L L^T, lower-triangular L. Right-looking blocked: host chol of
     the (symmetrized, as the reference does) diagonal block, panel scale
     L21 = A21 L11^-T and trailing A22 -= L21 L21^T as device-resident
-    engine GEMMs; signs folded into the host factor."""
+    engine GEMMs. panel="inverse" (the default) scales the panel by the
+    host inverse of L11, signs folded into the host factor;
+    panel="trsm" solves it on the device instead (Engine.trsm_raw), with
+    no inverse formed and L11 uploaded once."""
     from .api import BlockMatrix
 
+    if panel not in ("inverse", "trsm"):
+        raise ValueError(f"panel must be 'inverse' or 'trsm': {panel!r}")
     a = dvm.toBreeze()
     n = a.shape[0]
     if a.shape[0] != a.shape[1]:
@@ -230,6 +354,12 @@ def cholesky_decompose(dvm, mode="auto", base_size=1000, grouped=True):
 
     eng = dvm._engine()
     nb, offs, lens = _split(n, base_size)
+    if panel == "trsm":
+        host = _cholesky_trsm(eng, a, nb, offs, lens)
+        for i in range(nb):
+            for j in range(i + 1, nb):
+                host[(i, j)] = np.zeros((lens[i], lens[j]))
+        return BlockMatrix(host, n, n, engine=dvm._eng)
     blk = {(i, j): eng.upload_matrix(a[offs[i]:offs[i] + lens[i],
                                        offs[j]:offs[j] + lens[j]])
            for i in range(nb) for j in range(nb) if i >= j}
