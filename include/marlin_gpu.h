@@ -70,6 +70,11 @@ int mx_device_info(mx_ctx* ctx, int* cus, int* clock_khz);
 int mx_grid(mx_ctx* ctx, int* pr, int* pc, int* prow, int* pcol);
 
 /* ---- whole-multiply entries (the BlockMatrix.multiply replacement) ------ */
+/* Every entry that takes host buffers (the multiplies, SUMMA and k-resident
+ * host entries below, mx_tile_dgemm_acc, mx_map, mx_sum, mx_transpose,
+ * mx_dgemv) stages them into padded device images: a call with an image
+ * whose size in bytes does not fit int64_t returns MX_ENOMEM before it
+ * touches the device. */
 /* Single-GPU: C = A * B, host col-major buffers; the engine does
  * pad/H2D/tiled MFMA GEMM/D2H internally. */
 int mx_dgemm(mx_ctx* ctx, int64_t m, int64_t k, int64_t n,

@@ -25,7 +25,7 @@
 #include <utility>
 
 #include "../../include/marlin_gpu.h"
-#include "gemm_op_layout.h"
+#include "host_stage.h"          // the staging of the host-buffer entries
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
 #include "gemm_splitk_plan.h"  // the split-K slicing policy
 #include "trsm_plan.h"         // the triangular solve: check and step list
@@ -79,12 +79,22 @@ static shard_t local_shard(int64_t m, int64_t n, int pr, int pc, int prow,
   return {mi, nj, round_up(mi, 128), round_up(nj, 128)};
 }
 
+// The roles of the context's events.
+enum mx_event {
+  EV_TIMED_BEGIN, EV_TIMED_END,        // timed(): around what it enqueues
+  EV_H2D_BEGIN, EV_H2D_END,            // gemm_host: around the stage-in
+  EV_D2H,                              // gemm_host: kernel done, download
+  EV_GEMM_DONE0, EV_GEMM_DONE1,        // SUMMA: GEMM done with panel buffer b
+  EV_PANEL_READY0, EV_PANEL_READY1,    // SUMMA: panel buffer b packed
+  EV_COUNT
+};
+
 struct mx_ctx {
   int device = 0;
   hipStream_t s_gemm = nullptr;
   hipStream_t s_copy = nullptr;
   hipStream_t s_comm = nullptr;
-  hipEvent_t ev[16] = {};
+  hipEvent_t ev[EV_COUNT] = {};
   // distributed
   int rank = 0, nranks = 1;
   int pr = 1, pc = 1, prow = 0, pcol = 0;
@@ -135,7 +145,7 @@ const char* mx_strerror(int code) {
 // destroys the streams/events a ctx created (a partially-initialised one
 // included) and the ctx itself
 static void ctx_teardown(mx_ctx* c) {
-  for (int i = 0; i < 16; i++)
+  for (int i = 0; i < EV_COUNT; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   if (c->s_gemm) (void)hipStreamDestroy(c->s_gemm);
   if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
@@ -156,7 +166,7 @@ int mx_init(mx_ctx** out, int device) {
     ctx_teardown(c);
     return MX_EHIP;
   }
-  for (int i = 0; i < 16; i++)
+  for (int i = 0; i < EV_COUNT; i++)
     if (hipEventCreate(&c->ev[i]) != hipSuccess) { ctx_teardown(c); return MX_EHIP; }
   *out = c;
   return MX_OK;
@@ -343,18 +353,25 @@ static inline int launch_status(int rc) {
   return rc == 0 ? MX_OK : rc == -4 ? MX_EINVAL : MX_EHIP;
 }
 
-// One timed launch: enqueue() puts the GEMM on s_gemm and returns the
-// launcher's code; the event pair around it is waited for and its time and
-// the launch added to the stats.
+// enqueue() puts work on s_gemm and returns a launcher's code; the event
+// pair around it is waited for and its time added to the stats. Counting
+// the launches is the caller's.
+template <class Enqueue>
+static int timed(mx_ctx* c, Enqueue&& enqueue) {
+  HIP_OK(hipEventRecord(c->ev[EV_TIMED_BEGIN], c->s_gemm));
+  if (int rc = enqueue()) return launch_status(rc);
+  HIP_OK(hipEventRecord(c->ev[EV_TIMED_END], c->s_gemm));
+  HIP_OK(hipEventSynchronize(c->ev[EV_TIMED_END]));
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, c->ev[EV_TIMED_BEGIN], c->ev[EV_TIMED_END]));
+  c->st.gemm_ms += ms;
+  return MX_OK;
+}
+
+// One timed launch.
 template <class Enqueue>
 static int timed_gemm(mx_ctx* c, Enqueue&& enqueue) {
-  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  if (int rc = enqueue()) return launch_status(rc);
-  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-  HIP_OK(hipEventSynchronize(c->ev[1]));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->st.gemm_ms += ms;
+  if (int rc = timed(c, enqueue)) return rc;
   c->st.gemm_launches += 1;
   return MX_OK;
 }
@@ -595,27 +612,23 @@ int mx_trsm_device(mx_ctx* c, int is_fp32, int side, int lower, int trans,
   if ((rc = ensure(c, &c->wsT, plan.ws_elems * elem))) return rc;
   const char* tp = (const char*)dT->ptr;
   char* bp = (char*)dB->ptr;
-  HIP_OK(hipEventRecord(c->ev[0], c->s_gemm));
-  for (const mx_trsm_step& st : plan.steps) {
-    rc = mxk_trsm_diag(is_fp32, side, plan.tt, plan.rev, unit_diag, st.nv,
-                       tp + st.t_off * elem, ldt, bp + st.x_off * elem, ldb,
-                       c->wsT.ptr, r, c->s_gemm);
-    if (rc) return launch_status(rc);
-    if (st.rest_len == 0) continue;
-    const void* A = side ? c->wsT.ptr : (const void*)(tp + st.a_off * elem);
-    const void* B = side ? (const void*)(tp + st.b_off * elem) : c->wsT.ptr;
-    rc = mxk_gemm_op(is_fp32, 1, st.trans_a, st.trans_b, st.gm, st.gn, st.gk,
-                     A, st.lda, B, st.ldb, bp + st.c_off * elem, st.ldc,
-                     c->s_gemm);
-    if (rc) return launch_status(rc);
-    c->st.gemm_launches += 1;
-  }
-  HIP_OK(hipEventRecord(c->ev[1], c->s_gemm));
-  HIP_OK(hipEventSynchronize(c->ev[1]));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-  c->st.gemm_ms = ms;
-  return MX_OK;
+  return timed(c, [&] {               // the whole sweep; a launch per GEMM step
+    for (const mx_trsm_step& st : plan.steps) {
+      int e = mxk_trsm_diag(is_fp32, side, plan.tt, plan.rev, unit_diag, st.nv,
+                            tp + st.t_off * elem, ldt, bp + st.x_off * elem,
+                            ldb, c->wsT.ptr, r, c->s_gemm);
+      if (e) return e;
+      if (st.rest_len == 0) continue;
+      const void* A = side ? c->wsT.ptr : (const void*)(tp + st.a_off * elem);
+      const void* B = side ? (const void*)(tp + st.b_off * elem) : c->wsT.ptr;
+      e = mxk_gemm_op(is_fp32, 1, st.trans_a, st.trans_b, st.gm, st.gn, st.gk,
+                      A, st.lda, B, st.ldb, bp + st.c_off * elem, st.ldc,
+                      c->s_gemm);
+      if (e) return e;
+      c->st.gemm_launches += 1;
+    }
+    return 0;
+  });
 }
 
 // The mx_last_gemm_* entries: views of the one record kernels.hip keeps.
@@ -662,8 +675,50 @@ int mx_last_gemm_loop(mx_ctx* c, int* out) {
 }
 
 // ---------------------------------------------------------------------------
-// host-buffer whole-multiply entries: pad -> H2D -> kernel -> D2H.
-// elem = 8 (fp64) or 4 (fp32).
+// host-buffer entries: validate, lay out, stage in, run, stage out. The
+// images, their sizes and the copies are host_stage.h; this is its HIP
+// backend, bound to a stream and a direction.
+struct hip_stage {
+  hipStream_t s;
+  hipMemcpyKind kind;
+  int zero(void* p, int64_t bytes) {
+    HIP_OK(hipMemsetAsync(p, 0, (size_t)bytes, s));
+    return MX_OK;
+  }
+  int copy2d(void* dst, int64_t dpitch, const void* src, int64_t spitch,
+             int64_t width, int64_t cols) {
+    HIP_OK(hipMemcpy2DAsync(dst, (size_t)dpitch, src, (size_t)spitch,
+                            (size_t)width, (size_t)cols, kind, s));
+    return MX_OK;
+  }
+  int copy(void* dst, const void* src, int64_t bytes) {
+    HIP_OK(hipMemcpyAsync(dst, src, (size_t)bytes, kind, s));
+    return MX_OK;
+  }
+};
+
+// Size the image, grow the workspace to it and, given a host matrix, stage
+// it in on stream s (without one: room only).
+static int stage_ws(mx_ctx* c, mx_dbuf* ws, const mx_op_image& im,
+                    int64_t elem, const void* host = nullptr,
+                    hipStream_t s = nullptr) {
+  int64_t bytes;
+  if (!mx_image_bytes(im, elem, &bytes)) return MX_ENOMEM;
+  if (int rc = ensure(c, ws, bytes)) return rc;
+  hip_stage h2d = {s, hipMemcpyHostToDevice};
+  return host ? mx_stage_in(h2d, ws->ptr, im, elem, host) : MX_OK;
+}
+
+// Device image -> host matrix on stream s, complete on return.
+static int unstage(void* host, const void* dev, const mx_op_image& im,
+                   int64_t elem, hipStream_t s) {
+  hip_stage d2h = {s, hipMemcpyDeviceToHost};
+  if (int rc = mx_stage_out(d2h, host, dev, im, elem)) return rc;
+  HIP_OK(hipStreamSynchronize(s));
+  return MX_OK;
+}
+
+// Whole multiplies. elem = 8 (fp64) or 4 (fp32).
 // A is tight col-major m x k (k x m if trans_a), B k x n (n x k if
 // trans_b): each is uploaded as stored into its zero-padded image
 // (mx_gemm_op_layout), no transposed copy is made anywhere.
@@ -674,49 +729,42 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
   if (!c || !A || !B || !C) return MX_EINVAL;
   if ((trans_a | trans_b) & ~1) return MX_EINVAL;
   if (m <= 0 || k <= 0 || n <= 0) return MX_EDIM;
+  // the fused transpose(+add) epilogue is fp32, plain operands only
+  if (transpose_c && (!is_fp32 || trans_a || trans_b)) return MX_EINVAL;
+  if (!mx_op_can_round(m, k, n)) return MX_ENOMEM;
   const int64_t elem = is_fp32 ? 4 : 8;
   const int64_t mp = round_up(m, 128), np = round_up(n, 128),
                 kp = round_up(k, 16);
   mx_op_image ia, ib, ic;
   mx_gemm_op_layout(trans_a, trans_b, m, k, n, &ia, &ib, &ic);
+  const mx_op_image it = mx_epilogue_image(m, n, mp, np);  // add_c and C^T
+  if (!mx_images_fit(elem, {ia, ib, ic, it})) return MX_ENOMEM;
   c->st = {};
   c->st.flops = 2.0 * m * k * n;
   c->st.bytes_moved = (double)elem * (m * k + k * n + m * n);
 
   HIP_OK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, &c->wsA, mp * kp * elem))) return rc;
-  if ((rc = ensure(c, &c->wsB, kp * np * elem))) return rc;
-  if ((rc = ensure(c, &c->wsC, mp * np * elem))) return rc;
+  // room first: an allocation inside the timed window would count as h2d
+  if ((rc = stage_ws(c, &c->wsA, ia, elem))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, ib, elem))) return rc;
+  if ((rc = stage_ws(c, &c->wsC, ic, elem))) return rc;
 
-  HIP_OK(hipEventRecord(c->ev[2], c->s_copy));
-  if (ia.padded()) HIP_OK(hipMemsetAsync(c->wsA.ptr, 0, ia.elems() * elem, c->s_copy));
-  if (ib.padded()) HIP_OK(hipMemsetAsync(c->wsB.ptr, 0, ib.elems() * elem, c->s_copy));
-  HIP_OK(hipMemcpy2DAsync(c->wsA.ptr, ia.pitch * elem, A, ia.rows * elem,
-                          ia.rows * elem, ia.cols, hipMemcpyHostToDevice,
-                          c->s_copy));
-  HIP_OK(hipMemcpy2DAsync(c->wsB.ptr, ib.pitch * elem, B, ib.rows * elem,
-                          ib.rows * elem, ib.cols, hipMemcpyHostToDevice,
-                          c->s_copy));
-  if (beta_one) {
-    if (m != mp || n != np) HIP_OK(hipMemsetAsync(c->wsC.ptr, 0, mp * np * elem, c->s_copy));
-    HIP_OK(hipMemcpy2DAsync(c->wsC.ptr, mp * elem, C, m * elem, m * elem, n,
-                            hipMemcpyHostToDevice, c->s_copy));
-  }
-  HIP_OK(hipEventRecord(c->ev[3], c->s_copy));
-  HIP_OK(hipStreamWaitEvent(c->s_gemm, c->ev[3], 0));
+  HIP_OK(hipEventRecord(c->ev[EV_H2D_BEGIN], c->s_copy));
+  if ((rc = stage_ws(c, &c->wsA, ia, elem, A, c->s_copy))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, ib, elem, B, c->s_copy))) return rc;
+  if (beta_one && (rc = stage_ws(c, &c->wsC, ic, elem, C, c->s_copy)))
+    return rc;
+  HIP_OK(hipEventRecord(c->ev[EV_H2D_END], c->s_copy));
+  HIP_OK(hipStreamWaitEvent(c->s_gemm, c->ev[EV_H2D_END], 0));
 
   if (transpose_c) {
-    // fused transpose(+add) epilogue path (fp32 only): addC is N x M on
-    // host; stage it padded on device (reuse wsC tail? keep simple: own buf)
-    if (!is_fp32 || trans_a || trans_b) return MX_EINVAL;
+    // add_c is n x m on the host; the SUMMA panel buffer doubles as its
+    // staging area (no SUMMA call is in flight during a host multiply)
     const float* dAdd = nullptr;
     if (addC) {
-      if ((rc = ensure(c, &c->wsPA[0], np * mp * elem))) return rc;
-      if (n != np || m != mp)
-        HIP_OK(hipMemsetAsync(c->wsPA[0].ptr, 0, np * mp * elem, c->s_gemm));
-      HIP_OK(hipMemcpy2DAsync(c->wsPA[0].ptr, np * elem, addC, n * elem,
-                              n * elem, m, hipMemcpyHostToDevice, c->s_gemm));
+      if ((rc = stage_ws(c, &c->wsPA[0], it, elem, addC, c->s_gemm)))
+        return rc;
       dAdd = (const float*)c->wsPA[0].ptr;
     }
     rc = timed_gemm(c, [&] {
@@ -725,23 +773,18 @@ static int gemm_host(mx_ctx* c, int is_fp32, int beta_one, int64_t m,
                                    (float*)c->wsC.ptr, np, dAdd, c->s_gemm);
     });
     if (rc) return rc;
-    // C_out is n x m
-    HIP_OK(hipMemcpy2DAsync(C, n * elem, c->wsC.ptr, np * elem, n * elem, m,
-                            hipMemcpyDeviceToHost, c->s_gemm));
-    HIP_OK(hipStreamSynchronize(c->s_gemm));
+    if ((rc = unstage(C, c->wsC.ptr, it, elem, c->s_gemm))) return rc;
   } else {
     if ((rc = gemm_device(c, is_fp32, beta_one, mp, kp, np, c->wsA.ptr,
                           ia.pitch, c->wsB.ptr, ib.pitch, c->wsC.ptr,
                           ic.pitch, trans_a, trans_b)))
       return rc;
-    HIP_OK(hipEventRecord(c->ev[4], c->s_gemm));
-    HIP_OK(hipStreamWaitEvent(c->s_copy, c->ev[4], 0));
-    HIP_OK(hipMemcpy2DAsync(C, m * elem, c->wsC.ptr, mp * elem, m * elem, n,
-                            hipMemcpyDeviceToHost, c->s_copy));
-    HIP_OK(hipStreamSynchronize(c->s_copy));
+    HIP_OK(hipEventRecord(c->ev[EV_D2H], c->s_gemm));
+    HIP_OK(hipStreamWaitEvent(c->s_copy, c->ev[EV_D2H], 0));
+    if ((rc = unstage(C, c->wsC.ptr, ic, elem, c->s_copy))) return rc;
   }
   float h2d = 0;
-  HIP_OK(hipEventElapsedTime(&h2d, c->ev[2], c->ev[3]));
+  HIP_OK(hipEventElapsedTime(&h2d, c->ev[EV_H2D_BEGIN], c->ev[EV_H2D_END]));
   c->st.h2d_ms = h2d;
   c->st.total_ms = c->st.h2d_ms + c->st.gemm_ms;  // d2h folded into total sync
   return MX_OK;
@@ -949,9 +992,8 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
       return rc;
   }
 
-  // ev[8+b]: gemm done reading panel buffer b; ev[12+b]: panel b ready
-  HIP_OK(hipEventRecord(c->ev[8], c->s_gemm));
-  HIP_OK(hipEventRecord(c->ev[9], c->s_gemm));
+  HIP_OK(hipEventRecord(c->ev[EV_GEMM_DONE0], c->s_gemm));
+  HIP_OK(hipEventRecord(c->ev[EV_GEMM_DONE1], c->s_gemm));
 
   // deferred per-panel timing: events recorded in-loop, synchronised
   // only AFTER both streams drain (an in-loop sync would serialise the
@@ -968,7 +1010,7 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
 
     // comm stream: wait until the GEMM that read this buffer 2 panels ago
     // is done, then pack (root) and broadcast.
-    HIP_OK(hipStreamWaitEvent(c->s_comm, c->ev[8 + buf], 0));
+    HIP_OK(hipStreamWaitEvent(c->s_comm, c->ev[EV_GEMM_DONE0 + buf], 0));
     if ((rc = pack_panel(c, g, pan, k, elem, mip, nj, njp, pa, pb)))
       return rc;
     if (g.bcast) {
@@ -983,10 +1025,10 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
       HIP_OK(hipEventRecord(c1, c->s_comm));
       comm_tv.push_back({c0, c1});
     }
-    HIP_OK(hipEventRecord(c->ev[12 + buf], c->s_comm));
+    HIP_OK(hipEventRecord(c->ev[EV_PANEL_READY0 + buf], c->s_comm));
 
     // gemm stream: wait for the panel, accumulate
-    HIP_OK(hipStreamWaitEvent(c->s_gemm, c->ev[12 + buf], 0));
+    HIP_OK(hipStreamWaitEvent(c->s_gemm, c->ev[EV_PANEL_READY0 + buf], 0));
     if (has_tile) {
       int beta = p == 0 ? 0 : 1;
       hipEvent_t g0 = tev.mk(), g1 = tev.mk();
@@ -998,7 +1040,7 @@ static int summa_loop(mx_ctx* c, int is_fp32, const summa_pos& g, int64_t m,
       HIP_OK(hipEventRecord(g1, c->s_gemm));
       gemm_tv.push_back({g0, g1});
     }
-    HIP_OK(hipEventRecord(c->ev[8 + buf], c->s_gemm));
+    HIP_OK(hipEventRecord(c->ev[EV_GEMM_DONE0 + buf], c->s_gemm));
   }
   HIP_OK(hipStreamSynchronize(c->s_gemm));
   HIP_OK(hipStreamSynchronize(c->s_comm));
@@ -1113,47 +1155,6 @@ int mx_gemm_summa_kres_device(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
   return summa_kres_device(c, is_fp32, m, k, n, dA->ptr, dB->ptr, dC->ptr);
 }
 
-// host-buffer k-resident entry: shards are A_local mi x K, B_local K x nj
-// (tight col-major); engine pads and runs the single local GEMM.
-static int summa_kres_host(mx_ctx* c, int is_fp32, int64_t m, int64_t k,
-                           int64_t n, const void* A, const void* B, void* C) {
-  if (!c || !A || !B || !C) return MX_EINVAL;
-  if (!c->have_comm) return MX_ENOCOMM;
-  const int64_t elem = is_fp32 ? 4 : 8;
-  const auto [mi, nj, mip, njp] =
-      local_shard(m, n, c->pr, c->pc, c->prow, c->pcol);
-  const int64_t kp = round_up(k, 16);
-  if (mi == 0 || nj == 0) return MX_OK;
-  int rc;
-  HIP_OK(hipSetDevice(c->device));
-  if ((rc = ensure(c, &c->wsA, mip * kp * elem))) return rc;
-  if ((rc = ensure(c, &c->wsB, kp * njp * elem))) return rc;
-  if ((rc = ensure(c, &c->wsC, mip * njp * elem))) return rc;
-  if (mi != mip || k != kp)
-    HIP_OK(hipMemset(c->wsA.ptr, 0, (size_t)(mip * kp * elem)));
-  if (k != kp || nj != njp)
-    HIP_OK(hipMemset(c->wsB.ptr, 0, (size_t)(kp * njp * elem)));
-  HIP_OK(hipMemcpy2D(c->wsA.ptr, mip * elem, A, mi * elem, mi * elem, k,
-                     hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy2D(c->wsB.ptr, kp * elem, B, k * elem, k * elem, nj,
-                     hipMemcpyHostToDevice));
-  if ((rc = summa_kres_device(c, is_fp32, m, k, n, c->wsA.ptr, c->wsB.ptr,
-                              c->wsC.ptr)))
-    return rc;
-  HIP_OK(hipMemcpy2D(C, mi * elem, c->wsC.ptr, mip * elem, mi * elem, nj,
-                     hipMemcpyDeviceToHost));
-  return MX_OK;
-}
-
-int mx_dgemm_summa_kres(mx_ctx* c, int64_t m, int64_t k, int64_t n,
-                        const double* A, const double* B, double* C) {
-  return summa_kres_host(c, 0, m, k, n, A, B, C);
-}
-int mx_sgemm_summa_kres(mx_ctx* c, int64_t m, int64_t k, int64_t n,
-                        const float* A, const float* B, float* C) {
-  return summa_kres_host(c, 1, m, k, n, A, B, C);
-}
-
 int mx_dgemm_summa_device(mx_ctx* c, int64_t m, int64_t k, int64_t n,
                           const mx_dbuf* dA, const mx_dbuf* dB, mx_dbuf* dC) {
   if (!c || !dA || !dB || !dC) return MX_EINVAL;
@@ -1165,48 +1166,56 @@ int mx_sgemm_summa_device(mx_ctx* c, int64_t m, int64_t k, int64_t n,
   return summa_device(c, 1, m, k, n, dA->ptr, dB->ptr, dC->ptr);
 }
 
-// host-buffer SUMMA entries: pack local shards padded, H2D, run, D2H
-static int summa_host(mx_ctx* c, int is_fp32, int64_t m, int64_t k, int64_t n,
-                      const void* A, const void* B, void* C) {
+// host-buffer distributed entries on tight col-major shards: the panel loop
+// (A_local mi x kaj, B_local kbi x nj) or, kres, the k-resident layout
+// (A_local mi x K, B_local K x nj, one local GEMM).
+static int summa_host(mx_ctx* c, int is_fp32, bool kres, int64_t m, int64_t k,
+                      int64_t n, const void* A, const void* B, void* C) {
   if (!c || !A || !B || !C) return MX_EINVAL;
   if (!c->have_comm) return MX_ENOCOMM;
+  if (!mx_op_can_round(m, k, n)) return MX_ENOMEM;
   const int64_t elem = is_fp32 ? 4 : 8;
   const auto [mi, nj, mip, njp] =
       local_shard(m, n, c->pr, c->pc, c->prow, c->pcol);
-  const int64_t kaj = mx_slab_len(k, c->pc, c->pcol);
-  const int64_t kbi = mx_slab_len(k, c->pr, c->prow);
-  const int64_t kbi_p = round_up(kbi, 16);
-  int rc;
+  mx_op_image ia, ib, ic;
+  if (kres)
+    mx_summa_kres_layout(mi, nj, mip, njp, k, round_up(k, 16), &ia, &ib, &ic);
+  else
+    mx_summa_host_layout(mi, nj, mip, njp, mx_slab_len(k, c->pc, c->pcol),
+                         mx_slab_len(k, c->pr, c->prow), &ia, &ib, &ic);
+  if (!mx_images_fit(elem, {ia, ib, ic})) return MX_ENOMEM;
   HIP_OK(hipSetDevice(c->device));
-  if ((rc = ensure(c, &c->wsA, mip * (kaj > 0 ? kaj : 1) * elem))) return rc;
-  if ((rc = ensure(c, &c->wsB, kbi_p * (nj > 0 ? nj : 1) * elem))) return rc;
-  if ((rc = ensure(c, &c->wsC, mip * njp * elem))) return rc;
-  if (mi != mip && kaj > 0)
-    HIP_OK(hipMemset(c->wsA.ptr, 0, (size_t)(mip * kaj * elem)));
-  if (kbi != kbi_p && nj > 0)
-    HIP_OK(hipMemset(c->wsB.ptr, 0, (size_t)(kbi_p * nj * elem)));
-  if (mi > 0 && kaj > 0)
-    HIP_OK(hipMemcpy2D(c->wsA.ptr, mip * elem, A, mi * elem, mi * elem, kaj,
-                       hipMemcpyHostToDevice));
-  if (kbi > 0 && nj > 0)
-    HIP_OK(hipMemcpy2D(c->wsB.ptr, kbi_p * elem, B, kbi * elem, kbi * elem,
-                       nj, hipMemcpyHostToDevice));
-  if ((rc = summa_device(c, is_fp32, m, k, n, c->wsA.ptr, c->wsB.ptr,
-                         c->wsC.ptr)))
+  int rc;
+  // an empty k-resident shard stages nothing: the device entry sets the stats
+  if (!(kres && ic.empty())) {
+    if ((rc = stage_ws(c, &c->wsA, ia, elem, A, c->s_copy))) return rc;
+    if ((rc = stage_ws(c, &c->wsB, ib, elem, B, c->s_copy))) return rc;
+    if ((rc = stage_ws(c, &c->wsC, ic, elem))) return rc;
+    // complete, not merely ordered: summa_loop packs panels on s_comm
+    // straight out of wsA and wsB
+    HIP_OK(hipStreamSynchronize(c->s_copy));
+  }
+  if ((rc = (kres ? summa_kres_device : summa_device)(
+           c, is_fp32, m, k, n, c->wsA.ptr, c->wsB.ptr, c->wsC.ptr)))
     return rc;
-  if (mi > 0 && nj > 0)
-    HIP_OK(hipMemcpy2D(C, mi * elem, c->wsC.ptr, mip * elem, mi * elem, nj,
-                       hipMemcpyDeviceToHost));
-  return MX_OK;
+  return unstage(C, c->wsC.ptr, ic, elem, c->s_copy);
 }
 
 int mx_dgemm_summa(mx_ctx* c, int64_t m, int64_t k, int64_t n,
                    const double* A, const double* B, double* C) {
-  return summa_host(c, 0, m, k, n, A, B, C);
+  return summa_host(c, 0, false, m, k, n, A, B, C);
 }
 int mx_sgemm_summa(mx_ctx* c, int64_t m, int64_t k, int64_t n, const float* A,
                    const float* B, float* C) {
-  return summa_host(c, 1, m, k, n, A, B, C);
+  return summa_host(c, 1, false, m, k, n, A, B, C);
+}
+int mx_dgemm_summa_kres(mx_ctx* c, int64_t m, int64_t k, int64_t n,
+                        const double* A, const double* B, double* C) {
+  return summa_host(c, 0, true, m, k, n, A, B, C);
+}
+int mx_sgemm_summa_kres(mx_ctx* c, int64_t m, int64_t k, int64_t n,
+                        const float* A, const float* B, float* C) {
+  return summa_host(c, 1, true, m, k, n, A, B, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -1219,22 +1228,16 @@ int mx_map(mx_ctx* c, int op, int is_fp32, int64_t n, const void* A,
   const int binary = mx_aux_map_binary(op);
   if (binary && !B) return MX_EINVAL;
   const int64_t elem = is_fp32 ? 4 : 8;
+  mx_op_image im;
+  if (!mx_flat_image(n, 1, &im) || !mx_images_fit(elem, {im})) return MX_ENOMEM;
   HIP_OK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, &c->wsA, n * elem))) return rc;
-  if (binary && (rc = ensure(c, &c->wsB, n * elem))) return rc;
-  HIP_OK(hipMemcpyAsync(c->wsA.ptr, A, n * elem, hipMemcpyHostToDevice,
-                        c->s_gemm));
-  if (binary)
-    HIP_OK(hipMemcpyAsync(c->wsB.ptr, B, n * elem, hipMemcpyHostToDevice,
-                          c->s_gemm));
+  if ((rc = stage_ws(c, &c->wsA, im, elem, A, c->s_gemm))) return rc;
+  if (binary && (rc = stage_ws(c, &c->wsB, im, elem, B, c->s_gemm))) return rc;
   if ((rc = mxk_map(is_fp32, op, n, c->wsA.ptr, binary ? c->wsB.ptr : nullptr,
                     scalar, c->wsA.ptr, c->s_gemm)))
     return MX_EHIP;
-  HIP_OK(hipMemcpyAsync(C, c->wsA.ptr, n * elem, hipMemcpyDeviceToHost,
-                        c->s_gemm));
-  HIP_OK(hipStreamSynchronize(c->s_gemm));
-  return MX_OK;
+  return unstage(C, c->wsA.ptr, im, elem, c->s_gemm);
 }
 
 // mx_map on device buffers: the same kernel, nothing crosses PCIe.
@@ -1259,59 +1262,55 @@ int mx_map_device(mx_ctx* c, int op, int is_fp32, int64_t n, const mx_dbuf* dA,
 int mx_sum(mx_ctx* c, int is_fp32, int64_t n, const void* A, double* out) {
   if (!c || !A || !out || n <= 0) return MX_EINVAL;
   const int64_t elem = is_fp32 ? 4 : 8;
+  mx_op_image im;
+  if (!mx_flat_image(n, 1, &im) || !mx_images_fit(elem, {im})) return MX_ENOMEM;
+  const mx_op_image parts_im = {1024 + 1, 1, 1024 + 1, 1}, one = {1, 1, 1, 1};
   HIP_OK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, &c->wsA, n * elem))) return rc;
-  if ((rc = ensure(c, &c->wsB, (1024 + 1) * 8))) return rc;
-  HIP_OK(hipMemcpyAsync(c->wsA.ptr, A, n * elem, hipMemcpyHostToDevice,
-                        c->s_gemm));
+  if ((rc = stage_ws(c, &c->wsA, im, elem, A, c->s_gemm))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, parts_im, 8))) return rc;
   double* parts = (double*)c->wsB.ptr;
   if ((rc = mxk_sum(is_fp32, n, c->wsA.ptr, parts, parts + 1024, c->s_gemm)))
     return MX_EHIP;
-  HIP_OK(hipMemcpyAsync(out, parts + 1024, 8, hipMemcpyDeviceToHost,
-                        c->s_gemm));
-  HIP_OK(hipStreamSynchronize(c->s_gemm));
-  return MX_OK;
+  return unstage(out, parts + 1024, one, 8, c->s_gemm);
 }
 
 int mx_transpose(mx_ctx* c, int is_fp32, int64_t m, int64_t n, const void* A,
                  void* C) {
   if (!c || !A || !C || m <= 0 || n <= 0) return MX_EINVAL;
   const int64_t elem = is_fp32 ? 4 : 8;
+  mx_op_image im;
+  if (!mx_flat_image(m, n, &im) || !mx_images_fit(elem, {im})) return MX_ENOMEM;
   HIP_OK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, &c->wsA, m * n * elem))) return rc;
-  if ((rc = ensure(c, &c->wsB, m * n * elem))) return rc;
-  HIP_OK(hipMemcpyAsync(c->wsA.ptr, A, m * n * elem, hipMemcpyHostToDevice,
-                        c->s_gemm));
+  if ((rc = stage_ws(c, &c->wsA, im, elem, A, c->s_gemm))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, im, elem))) return rc;
   if ((rc = mxk_transpose(is_fp32, m, n, c->wsA.ptr, c->wsB.ptr, c->s_gemm)))
     return MX_EHIP;
-  HIP_OK(hipMemcpyAsync(C, c->wsB.ptr, m * n * elem, hipMemcpyDeviceToHost,
-                        c->s_gemm));
-  HIP_OK(hipStreamSynchronize(c->s_gemm));
-  return MX_OK;
+  return unstage(C, c->wsB.ptr, im, elem, c->s_gemm);
 }
 
 // Matrix-vector multiply (BlockMatrix.scala:240-274): y = A x.
 int mx_dgemv(mx_ctx* c, int64_t m, int64_t n, const double* A,
              const double* x, double* y) {
   if (!c || !A || !x || !y || m <= 0 || n <= 0) return MX_EINVAL;
+  mx_op_image ia;
+  if (!mx_flat_image(m, n, &ia) || !mx_images_fit(8, {ia})) return MX_ENOMEM;
+  // wsB holds x then y (m * n fits, so n + m does); wsC 32 chunk partials
+  const mx_op_image ix = {n, 1, n, 1}, iy = {m, 1, m, 1},
+                    ixy = {n + m, 1, n + m, 1}, iparts = {m, 32, m, 32};
+  if (!mx_images_fit(8, {ixy, iparts})) return MX_ENOMEM;
   HIP_OK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure(c, &c->wsA, m * n * 8))) return rc;
-  if ((rc = ensure(c, &c->wsB, (n + m) * 8))) return rc;
-  if ((rc = ensure(c, &c->wsC, 32 * m * 8))) return rc;  // 32 chunk partials
-  HIP_OK(hipMemcpyAsync(c->wsA.ptr, A, m * n * 8, hipMemcpyHostToDevice,
-                        c->s_gemm));
-  HIP_OK(hipMemcpyAsync(c->wsB.ptr, x, n * 8, hipMemcpyHostToDevice,
-                        c->s_gemm));
+  if ((rc = stage_ws(c, &c->wsA, ia, 8, A, c->s_gemm))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, ixy, 8))) return rc;
+  if ((rc = stage_ws(c, &c->wsB, ix, 8, x, c->s_gemm))) return rc;
+  if ((rc = stage_ws(c, &c->wsC, iparts, 8))) return rc;
   double* dy = (double*)c->wsB.ptr + n;
   if ((rc = mxk_gemv(0, m, n, m, c->wsA.ptr, c->wsB.ptr, (double*)c->wsC.ptr,
                      dy, c->s_gemm)))
     return MX_EHIP;
-  HIP_OK(hipMemcpyAsync(y, dy, m * 8, hipMemcpyDeviceToHost, c->s_gemm));
-  HIP_OK(hipStreamSynchronize(c->s_gemm));
-  return MX_OK;
+  return unstage(y, dy, iy, 8, c->s_gemm);
 }
 
 // Device-resident gemv on a cached matrix (x, y host vectors; the

@@ -315,9 +315,10 @@ class Engine:
         return tuple(v.value for v in vals)  # pr, pc, prow, pcol
 
     # -- whole multiplies ----------------------------------------------------
-    def _gemm_op(self, A, B, dt, trans_a, trans_b):
-        """C = op(A)·op(B) through mx_gemm_op: A, B are passed as stored
-        (A is k x m where trans_a, B is n x k where trans_b)."""
+    def _gemm_op(self, A, B, dt, trans_a=False, trans_b=False):
+        """C = op(A)·op(B) on host arrays: A, B are passed as stored (A is
+        k x m where trans_a, B is n x k where trans_b). mx_dgemm and
+        mx_sgemm are the plain form of the entry called here."""
         A = np.asfortranarray(A, dtype=dt)
         B = np.asfortranarray(B, dtype=dt)
         m, k, n = gemm_op_shape(A.shape, B.shape, trans_a, trans_b)
@@ -331,41 +332,17 @@ class Engine:
         return C
 
     def dgemm(self, A, B, trans_a=False, trans_b=False):
-        if trans_a or trans_b:
-            return self._gemm_op(A, B, np.float64, trans_a, trans_b)
-        A = np.asfortranarray(A, dtype=np.float64)
-        B = np.asfortranarray(B, dtype=np.float64)
-        m, k = A.shape
-        k2, n = B.shape
-        if k != k2:
-            raise ValueError(
-                f"Dimension mismatch during matrix-matrix multiplication: "
-                f"{k} vs {k2}")
-        C = np.empty((m, n), dtype=np.float64, order="F")
-        _ck(lib().mx_dgemm(self._ctx, m, k, n, _fbuf(A, np.float64),
-                           _fbuf(B, np.float64), _fbuf(C, np.float64)),
-            "mx_dgemm")
-        if _LOG:
+        C = self._gemm_op(A, B, np.float64, trans_a, trans_b)
+        if _LOG and not (trans_a or trans_b):
             st = self.stats()
+            (m, n), k = C.shape, np.shape(A)[1]
             _log(f"dgemm {m}x{k}x{n}: gemm {st['gemm_ms']:.2f} ms "
                  f"(h2d {st['h2d_ms']:.2f} ms, "
                  f"{st['flops'] / max(st['gemm_ms'], 1e-9) / 1e9:.1f} TF/s)")
         return C
 
     def sgemm(self, A, B, trans_a=False, trans_b=False):
-        if trans_a or trans_b:
-            return self._gemm_op(A, B, np.float32, trans_a, trans_b)
-        A = np.asfortranarray(A, dtype=np.float32)
-        B = np.asfortranarray(B, dtype=np.float32)
-        m, k = A.shape
-        _, n = B.shape
-        if A.shape[1] != B.shape[0]:
-            raise ValueError("Dimension mismatch during matrix-matrix multiplication")
-        C = np.empty((m, n), dtype=np.float32, order="F")
-        _ck(lib().mx_sgemm(self._ctx, m, k, n, _fbuf(A, np.float32),
-                           _fbuf(B, np.float32), _fbuf(C, np.float32)),
-            "mx_sgemm")
-        return C
+        return self._gemm_op(A, B, np.float32, trans_a, trans_b)
 
     def sgemm_transpose_add(self, A, B, add_c=None):
         """C = (A*B)^T (+ add_c) with the epilogue fused on-device."""
@@ -400,18 +377,34 @@ class Engine:
                                     beta), "mx_tile_dgemm_acc")
         return C
 
+    def _summa_host(self, name, dt, m, k, n, A_local, B_local):
+        """One of the host-buffer distributed entries on this rank's
+        shards: returns this rank's mi x nj block of C."""
+        A_local = np.asfortranarray(A_local, dtype=dt)
+        B_local = np.asfortranarray(B_local, dtype=dt)
+        pr, pc, prow, pcol = self.grid()
+        C = np.empty((slab_len(m, pr, prow), slab_len(n, pc, pcol)), dtype=dt,
+                     order="F")
+        _ck(getattr(lib(), name)(self._ctx, m, k, n, _fbuf(A_local, dt),
+                                 _fbuf(B_local, dt), _fbuf(C, dt)), name)
+        return C
+
     def dgemm_summa(self, m, k, n, A_local, B_local):
         """Distributed multiply on this rank's shards (after comm_init)."""
-        A_local = np.asfortranarray(A_local, dtype=np.float64)
-        B_local = np.asfortranarray(B_local, dtype=np.float64)
-        pr, pc, prow, pcol = self.grid()
-        mi = slab_len(m, pr, prow)
-        nj = slab_len(n, pc, pcol)
-        C = np.empty((mi, nj), dtype=np.float64, order="F")
-        _ck(lib().mx_dgemm_summa(self._ctx, m, k, n, _fbuf(A_local, np.float64),
-                                 _fbuf(B_local, np.float64),
-                                 _fbuf(C, np.float64)), "mx_dgemm_summa")
-        return C
+        return self._summa_host("mx_dgemm_summa", np.float64, m, k, n,
+                                A_local, B_local)
+
+    def sgemm_summa(self, m, k, n, A_local, B_local):
+        """fp32 distributed multiply on this rank's shards."""
+        return self._summa_host("mx_sgemm_summa", np.float32, m, k, n,
+                                A_local, B_local)
+
+    def dgemm_summa_kres(self, m, k, n, A_local, B_local):
+        """k-resident distributed multiply (config-4 layout): A_local is
+        this rank's row slab with ALL k columns, B_local its col slab
+        with ALL k rows; one local GEMM, zero collectives."""
+        return self._summa_host("mx_dgemm_summa_kres", np.float64, m, k, n,
+                                A_local, B_local)
 
     # -- elementwise / reduction / transpose (epilogue-op family) ----------
     OPS = {"add": 0, "sub": 1, "emul": 2, "adds": 3, "subs": 4, "rsubs": 5,
@@ -466,37 +459,6 @@ class Engine:
                                A.ctypes.data_as(ctypes.c_void_p),
                                C.ctypes.data_as(ctypes.c_void_p)),
             "mx_transpose")
-        return C
-
-    def sgemm_summa(self, m, k, n, A_local, B_local):
-        """fp32 distributed multiply on this rank's shards."""
-        A_local = np.asfortranarray(A_local, dtype=np.float32)
-        B_local = np.asfortranarray(B_local, dtype=np.float32)
-        pr, pc, prow, pcol = self.grid()
-        mi = slab_len(m, pr, prow)
-        nj = slab_len(n, pc, pcol)
-        C = np.empty((mi, nj), dtype=np.float32, order="F")
-        _ck(lib().mx_sgemm_summa(self._ctx, m, k, n,
-                                 _fbuf(A_local, np.float32),
-                                 _fbuf(B_local, np.float32),
-                                 _fbuf(C, np.float32)), "mx_sgemm_summa")
-        return C
-
-    def dgemm_summa_kres(self, m, k, n, A_local, B_local):
-        """k-resident distributed multiply (config-4 layout): A_local is
-        this rank's row slab with ALL k columns, B_local its col slab
-        with ALL k rows; one local GEMM, zero collectives."""
-        A_local = np.asfortranarray(A_local, dtype=np.float64)
-        B_local = np.asfortranarray(B_local, dtype=np.float64)
-        pr, pc, prow, pcol = self.grid()
-        mi = slab_len(m, pr, prow)
-        nj = slab_len(n, pc, pcol)
-        C = np.empty((mi, nj), dtype=np.float64, order="F")
-        _ck(lib().mx_dgemm_summa_kres(self._ctx, m, k, n,
-                                      _fbuf(A_local, np.float64),
-                                      _fbuf(B_local, np.float64),
-                                      _fbuf(C, np.float64)),
-            "mx_dgemm_summa_kres")
         return C
 
     def gemm_summa_kres_device(self, m, k, n, dA, dB, dC, fp32=False):

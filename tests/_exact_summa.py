@@ -283,17 +283,20 @@ def run_real_device(eng, c, entry, keep=None):
             eng.free(d)
 
 
-def run_real_host(eng, c, entry, keep=None):
+def run_real_host(eng, c, entry, keep=None, poison=None):
     """One real one-rank host entry on tight col-major operands: 'summa'
     (mx_[ds]gemm_summa) or 'kres' (mx_[ds]gemm_summa_kres). The host
     entries return the logical block only, so there are no pads to
-    check."""
+    check. poison: called with the engine right before the entry, to
+    dirty the cached workspaces the entry stages into."""
     import ctypes
     from marlin_amd import engine as E
     assert (c.pr, c.pc) == (1, 1)
     dt = dtype_of(c.fp32)
     a, b, ref = summa_inputs(c.fp32, c.m, c.k, c.n)[:3]
     got = _filled(c.m, c.n, _nan(dt))
+    if poison is not None:
+        poison(eng)
     name = "mx_%sgemm_summa%s" % ("s" if c.fp32 else "d",
                                   "_kres" if entry == "kres" else "")
     rc = getattr(E.lib(), name)(eng._ctx, c.m, c.k, c.n, E._fbuf(a, dt),

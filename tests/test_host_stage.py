@@ -1,7 +1,8 @@
-# Host side of mx_gemm_op without a GPU: the padding arithmetic, pitches
-# and copy extents (marlin_amd/csrc/gemm_op_layout.h) replayed on heap
-# buffers by a stand-alone program built under AddressSanitizer
-# (tests/data/gemm_op_layout_check.cpp), with the sanitizer runtime linked
+# The staging of the host-buffer entries without a GPU: the images, their
+# byte sizes and the stage-in / stage-out code of
+# marlin_amd/csrc/host_stage.h, run with a heap backend by a stand-alone
+# program built under AddressSanitizer + UBSan
+# (tests/data/host_stage_check.cpp), with the sanitizer runtime linked
 # statically into the program so that it needs nothing from its
 # environment. Where the toolchain cannot link the sanitizer the same
 # program is built plain: its own extent and value checks still run.
@@ -10,7 +11,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "data", "gemm_op_layout_check.cpp")
+SRC = os.path.join(HERE, "data", "host_stage_check.cpp")
 INC = os.path.join(ROOT, "marlin_amd", "csrc")
 
 
@@ -20,8 +21,8 @@ def _build(exe, flags):
                           capture_output=True, text=True)
 
 
-def test_gemm_op_host_layout_under_asan(tmp_path):
-    exe = str(tmp_path / "layout_check")
+def test_host_stage_under_asan(tmp_path):
+    exe = str(tmp_path / "host_stage_check")
     r = _build(exe, ["-fsanitize=address,undefined", "-static-libasan",
                      "-static-libubsan",
                      "-fno-sanitize-recover=all"])
@@ -30,4 +31,6 @@ def test_gemm_op_host_layout_under_asan(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, (run.stdout + run.stderr)[-2000:]
+    # the 28 multiply forms, then every other image and the size sweep
     assert "gemm_op_layout OK 28" in run.stdout
+    assert "host_stage OK 616 images 3248 size checks" in run.stdout
