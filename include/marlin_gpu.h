@@ -69,6 +69,32 @@ int mx_device_info(mx_ctx* ctx, int* cus, int* clock_khz);
 /* Grid geometry of this rank after mx_comm_init (pr,pc,row,col). */
 int mx_grid(mx_ctx* ctx, int* pr, int* pc, int* prow, int* pcol);
 
+/* ---- numerics of the GEMM and gemv entries ------------------------------ */
+/* Every entry below that multiplies (host and device GEMMs in every op form
+ * and kernel geometry, the fused epilogue, grouped, split-K, SUMMA, the
+ * per-tile accumulate, gemv) computes in the element type with IEEE
+ * round-to-nearest: full-width operands, an accumulator of the element
+ * type (fp64 in gemv), plain adds in the epilogue and the split-K fold.
+ * For every element of a result C^ of R = op(A)·op(B) (+ C0 | + add_c), with
+ * S = |op(A)|·|op(B)| (+ |C0| | + |add_c|), u = 2^-24 (fp32) or 2^-53 (fp64):
+ *
+ *     |C^ - R| <= g(terms) * S + 2 * terms * eta,   g(t) = t*u / (1 - t*u)
+ *
+ *   - terms is the number of summands of the element: k for a product,
+ *     k + 1 when accumulating or adding add_c, the sum of the k's over an
+ *     mx_tile_dgemm_acc chain, k for a SUMMA panel loop (the chain continues
+ *     across panels), n for gemv;
+ *   - split-K with S slices changes the order of the sum (S chains, then a
+ *     fold in slice order) and adds S to terms: k + S;
+ *   - eta is half the smallest subnormal (2^-150, 2^-1075): subnormal inputs,
+ *     products and results are honoured, never flushed, so this is all that
+ *     underflow can cost; where S is 0 the result is exactly 0;
+ *   - +-inf and NaN propagate as IEEE sums of products do (0 * inf is NaN).
+ * The bound holds for any summation order, fused or not, so it does not
+ * depend on a knob, a geometry or the schedule; which order a given entry
+ * uses, and that it is fixed, is stated with the entry.
+ * tests/test_gpu_gemm_rounding.py holds every entry to it, componentwise. */
+
 /* ---- whole-multiply entries (the BlockMatrix.multiply replacement) ------ */
 /* Every entry that takes host buffers (the multiplies, SUMMA and k-resident
  * host entries below, mx_tile_dgemm_acc, mx_map, mx_sum, mx_transpose,

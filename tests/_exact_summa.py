@@ -92,12 +92,14 @@ class Geometry:
         self.empty = self.mi == 0 or self.nj == 0
 
 
-def a_shard(c, prow, j):
+def a_shard(c, prow, j, a=None):
     """Image of A_local at (prow, j): mip x (kaj + 1), or None where the
-    shard has no rows or no k-columns."""
+    shard has no rows or no k-columns. a: the global A to cut instead of
+    the case's exact one (the rounding tests bring their own data)."""
     from marlin_amd import engine as E
     dt = dtype_of(c.fp32)
-    a = summa_inputs(c.fp32, c.m, c.k, c.n)[0]
+    if a is None:
+        a = summa_inputs(c.fp32, c.m, c.k, c.n)[0]
     mi, mo = E.slab_len(c.m, c.pr, prow), E.slab_off(c.m, c.pr, prow)
     kaj, ko = E.slab_len(c.k, c.pc, j), E.slab_off(c.k, c.pc, j)
     if mi == 0 or kaj == 0:
@@ -108,12 +110,14 @@ def a_shard(c, prow, j):
     return img
 
 
-def b_shard(c, i, pcol):
+def b_shard(c, i, pcol, b=None):
     """Image of B_local at (i, pcol): roundup(kbi,16) x (nj + 1), pad rows
-    and guard column the NaN sentinel; None where the shard is empty."""
+    and guard column the NaN sentinel; None where the shard is empty. b:
+    the global B to cut instead of the case's exact one."""
     from marlin_amd import engine as E
     dt = dtype_of(c.fp32)
-    b = summa_inputs(c.fp32, c.m, c.k, c.n)[1]
+    if b is None:
+        b = summa_inputs(c.fp32, c.m, c.k, c.n)[1]
     kbi, ko = E.slab_len(c.k, c.pr, i), E.slab_off(c.k, c.pr, i)
     nj, no = E.slab_len(c.n, c.pc, pcol), E.slab_off(c.n, c.pc, pcol)
     if kbi == 0 or nj == 0:
