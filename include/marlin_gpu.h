@@ -439,6 +439,65 @@ int mx_trsm_device(mx_ctx* ctx, int is_fp32, int side, int lower, int trans,
                    int unit_diag, int64_t n, int64_t r,
                    const mx_dbuf* dT, int64_t ldt, mx_dbuf* dB, int64_t ldb);
 
+/* LU factorisation on a device image, in place: blocked, right-looking,
+ * with the row permutation kept on the device. No host step and no PCIe
+ * traffic inside the sweep; the factor stays where mx_trsm_device reads it.
+ *
+ * Layout. The order-n matrix is a column-major image of np rows and np
+ * columns, np = n rounded up to 128, at pitch lda >= np, a multiple of 16
+ * bytes. The pads (rows and columns [n, np)) must be zero on entry and are
+ * zero on exit: the image Engine.upload_matrix makes. On return the image
+ * holds packed L\U, L unit-lower and U upper, the form mx_trsm_device reads
+ * as both factors. dPiv holds np int32: piv[g] for g < n is the source row
+ * of output row g, so that A[piv] == L * U with WHOLE rows moved (the L
+ * columns already finished are permuted with the rest; no fix-up remains
+ * for the host); piv[g] = g on the pad.
+ *
+ * Pivoting is partial pivoting INSIDE each 128 x 128 diagonal block, the
+ * reference's block-pivot scheme at the device's block width. In column j
+ * of a block the pivot is the entry of largest magnitude among the block's
+ * remaining rows; the test is |a| > best, so ties go to the lowest row
+ * index and a NaN is never chosen while another entry remains. Limitation:
+ * a pivot is never taken from another block row. A matrix whose diagonal
+ * block is singular, or nearly so, when its step comes is therefore not
+ * handled any better than the host path handles it at its base_size: an
+ * exactly zero pivot is reported through info, a tiny one is divided by.
+ *
+ * info. *info is 0 on success. If a pivot is exactly zero, *info is the
+ * 1-based global column of the FIRST such pivot; that column is left
+ * unscaled and the factorisation runs to the end, as LAPACK's does (U is
+ * then singular). The block itself is finished as stated; what lies below
+ * it is solved against its U (step 3 below), so from that column on the
+ * rows under the block, and the trailing matrix after them, hold inf / NaN.
+ * info travels through one 4-byte device word that is read back once, after
+ * the sweep.
+ *
+ * Algorithm, fixed so that the result does not depend on the schedule or
+ * the run. Step j (block offset o = 128 j), in stream order: (1) the
+ * diagonal kernel factors block (j, j) in LDS, elimination right-looking
+ * with ascending columns and rows, multiplier a / pivot, update by one
+ * fused multiply-add (marlin_amd/csrc/getrf_plan.h, mx_getrf_eliminate, is
+ * the statement), and writes its 128 permutation entries; (2) the
+ * row-permutation kernel applies them to rows [o, o + 128) of columns
+ * [0, o) and [o + 128, np); (3) L21 = A21 U11^-1 and (4) U12 = L11^-1 (P
+ * A12) by the triangular solve's diagonal kernel, the second leaving -U12
+ * in the context's workspace panel; (5) A22 += L21 * (-U12), one launch of
+ * the plain accumulating GEMM (k = 128). (3)-(5) only while blocks remain.
+ * No atomics.
+ *
+ * Checks. Everything is checked before anything is allocated or enqueued
+ * (getrf_plan.h is the code): the flag, n >= 0, NULL handles and a NULL
+ * info, the pitch, the image and the np * 4 bytes of dPiv against the sizes
+ * their buffers were allocated with (overflow-safely), and dA and dPiv as
+ * different handles whose device ranges share no byte. A refused call
+ * returns MX_EINVAL and has touched nothing (*info included). n == 0
+ * returns MX_OK with *info = 0 and looks at neither buffer.
+ *
+ * Stats: flops = 2 n^3 / 3, gemm_launches = the update GEMMs launched
+ * (np / 128 - 1), gemm_ms = event time over the whole sweep. */
+int mx_getrf_device(mx_ctx* ctx, int is_fp32, int64_t n, mx_dbuf* dA,
+                    int64_t lda, mx_dbuf* dPiv, int* info);
+
 /* Introspection: the gemm_mfma_kernel instantiation and remap arguments
  * of the most recent plain GEMM launch in this process (any entry that
  * reaches the kernel launcher; all zero before the first launch). The

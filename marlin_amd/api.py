@@ -247,11 +247,13 @@ class DenseVecMatrix:
         from .io import save_matrix_file
         save_matrix_file(self, path)
 
-    def luDecompose(self, mode="auto", base_size=1000, grouped=True):
+    def luDecompose(self, mode="auto", base_size=1000, grouped=True,
+                    panel="host"):
         """DenseVecMatrix.luDecompose (DenseVecMatrix.scala:283-464).
-        grouped=False keeps one launch per block product (same bits)."""
+        grouped=False keeps one launch per block product (same bits).
+        panel="device" factors wholly on the device (linalg.lu_decompose)."""
         from .linalg import lu_decompose
-        return lu_decompose(self, mode, base_size, grouped)
+        return lu_decompose(self, mode, base_size, grouped, panel)
 
     def inverse(self, mode="auto", base_size=1000, grouped=True):
         """DenseVecMatrix.inverse (DenseVecMatrix.scala:565-764).
@@ -311,12 +313,20 @@ class DenseVecMatrix:
         from .linalg import cholesky_decompose
         return cholesky_decompose(self, mode, base_size, grouped, panel)
 
-    def solve(self, rhs, mode="auto", base_size=1000):
+    def solve(self, rhs, mode="auto", base_size=1000, factor="host"):
         """x with A x = rhs (a vector, or a matrix of right-hand-side
         columns): luDecompose(mode, base_size), then two triangular solves
         on the device against the packed factor (linalg.lu_solve). No
-        inverse is formed."""
-        from .linalg import lu_decompose, lu_solve
+        inverse is formed. factor="device" factors on the device instead
+        (linalg.lu_factor_device, pivoting inside 128-wide diagonal
+        blocks; mode and base_size play no part) and solves against the
+        factor where it lies, with no second upload of it."""
+        from .linalg import lu_decompose, lu_factor_device, lu_solve
+        if factor not in ("host", "device"):
+            raise ValueError(f"factor must be 'host' or 'device': {factor!r}")
+        if factor == "device":
+            with lu_factor_device(self) as f:
+                return f.solve(rhs)
         blocks, p_array = lu_decompose(self, mode, base_size)
         if blocks._eng is None:
             blocks._eng = self._engine()

@@ -52,6 +52,15 @@ int mxk_splitk_reduce(int is_fp32, int64_t m, int64_t n, void* C, int64_t ldc,
 int mxk_trsm_diag(int is_fp32, int side, int tt, int rev, int unit, int nv,
                   const void* Tjj, int64_t ldt, void* X, int64_t ldx,
                   void* ws, int64_t r, hipStream_t stream);
+// One 128 x 128 diagonal block of mx_getrf_device, factored in place with
+// pivoting among its own rows (mx_getrf_eliminate, getrf_plan.h): piv gets
+// the block's 128 global source rows, *first_zero the 1-based global column
+// of a zero pivot if it still holds 0. Then that permutation applied to
+// rows [o, o + 128) of every other column of the np x np image.
+int mxk_getrf_diag(int is_fp32, int nv, int64_t o, void* Ajj, int64_t lda,
+                   int* piv, int* first_zero, hipStream_t stream);
+int mxk_getrf_rowperm(int is_fp32, int64_t o, int64_t np, void* A,
+                      int64_t lda, const int* piv, hipStream_t stream);
 int mxk_sgemm_tn_epilogue(int64_t M, int64_t N, int64_t K, const float* A,
                           int64_t lda, const float* B, int64_t ldb, float* C,
                           int64_t ldc, const float* addC, hipStream_t stream);

@@ -997,6 +997,183 @@ trsm_diag_kernel(const T* __restrict__ Tjj, int64_t ldt, T* __restrict__ X,
 }
 
 // ---------------------------------------------------------------------------
+// LU factorisation, the diagonal blocks and their row permutation
+// (mx_getrf_device; the sweep around them is getrf_plan.h, whose
+// mx_getrf_eliminate states the elimination these kernels perform: the
+// element operations below are that header's, in its order).
+//
+// getrf_diag_kernel factors ONE 128 x 128 block with partial pivoting among
+// its own rows. It is latency-bound by construction: one workgroup on one
+// CU, 128 dependent columns with three barriers each, so its cost is to be
+// compared with the host step it replaces (download, host LU, three
+// uploads), not with a roofline.
+//
+//   - The block lives whole in LDS, column-major at the odd pitch 129
+//     (fp64: 128 * 129 * 8 B = 132096 B of the 160 KB). The update and the
+//     scale walk a column with one row per lane (consecutive addresses); the
+//     row swap walks a row with one column per lane, a stride of 129
+//     elements, which the odd pitch spreads over all banks.
+//   - It moves between global memory and LDS in 16-byte chunks down the
+//     contiguous columns. Nothing at a row or column index >= nv is loaded
+//     or stored: the ragged block behaves as if continued by the identity,
+//     whose columns pivot on themselves and update nothing, so the loop
+//     ends at nv.
+//   - Column j: wave 0 alone finds the pivot (two rows per lane, a butterfly
+//     of mx_getrf_better over the wave, so no cross-wave step) and swaps
+//     the two rows (two columns per lane); then every remaining row is
+//     scaled by one division, then the rank-1 update runs over the whole
+//     workgroup, a row per thread and every fourth column.
+//   - No atomics, no cross-wave sums: the bits do not depend on the run.
+#define GETRF_FN __host__ __device__ __forceinline__
+#include "getrf_plan.h"
+
+constexpr int GETRF_W = 128;                     // order of a diagonal block
+constexpr int GETRF_P = GETRF_W + 1;             // pitch of the LDS image
+constexpr int GETRF_NT = 512;                    // threads of the workgroup
+constexpr int GETRF_CG = GETRF_NT / GETRF_W;     // column groups of the update
+constexpr int GETRF_CT = 8;                      // columns per row-perm tile
+
+// The leading nv x nv part of the block between global memory (pitch lda)
+// and the LDS image, 16-byte chunks down the columns; a chunk that crosses
+// nv goes element by element.
+template <typename T, int STORE>
+DEVFN void getrf_block_io(T* __restrict__ g, int64_t lda, T* S, int nv,
+                          int tid) {
+    using V = typename chunk16_t<T>::type;
+    constexpr int E = 16 / sizeof(T);
+    constexpr int CPC = GETRF_W / E;             // chunks per column
+    for (int q = tid; q < CPC * GETRF_W; q += GETRF_NT) {
+        const int r = (q % CPC) * E, c = q / CPC;
+        if (c >= nv || r >= nv) continue;
+        T* s = &S[r + c * GETRF_P];
+        T* p = g + r + (int64_t)c * lda;
+        if (r + E <= nv) {
+            V x;
+            if (!STORE) x = *reinterpret_cast<const V*>(p);
+            #pragma unroll
+            for (int e = 0; e < E; e++) {
+                if (STORE) x[e] = s[e]; else s[e] = x[e];
+            }
+            if (STORE) *reinterpret_cast<V*>(p) = x;
+        } else {
+            for (int e = 0; r + e < nv; e++) {
+                if (STORE) p[e] = s[e]; else s[e] = p[e];
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(GETRF_NT)
+getrf_diag_kernel(T* __restrict__ Ajj, int64_t lda, int nv, int o,
+                  int* __restrict__ piv, int* __restrict__ first_zero) {
+    __shared__ __attribute__((aligned(16))) T S[GETRF_W * GETRF_P];
+    __shared__ int perm[GETRF_W];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = tid % GETRF_W, cg = tid / GETRF_W;
+    if (tid < GETRF_W) perm[tid] = tid;
+    getrf_block_io<T, 0>(Ajj, lda, S, nv, tid);
+    int fz = 0;                          // thread 0's: first zero pivot, 1-based
+
+    #pragma unroll 1
+    for (int j = 0; j < nv; j++) {
+        T* colj = S + j * GETRF_P;
+        __syncthreads();                 // the update of column j - 1 is done
+        if (wave == 0) {
+            T key = T(-1);
+            int p = j;
+            #pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int i = lane + 64 * h;
+                if (i >= j && i < nv) {
+                    const T k2 = mx_getrf_key(colj[i]);
+                    if (mx_getrf_better(k2, i, key, p)) { key = k2; p = i; }
+                }
+            }
+            #pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const T k2 = __shfl_xor(key, d);
+                const int p2 = __shfl_xor(p, d);
+                if (mx_getrf_better(k2, p2, key, p)) { key = k2; p = p2; }
+            }
+            if (p != j) {                // wave-uniform
+                #pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int k = lane + 64 * h;
+                    if (k < nv) {
+                        const T a = S[j + k * GETRF_P], b = S[p + k * GETRF_P];
+                        S[j + k * GETRF_P] = b;
+                        S[p + k * GETRF_P] = a;
+                    }
+                }
+                if (lane == 0) {
+                    const int t = perm[j];
+                    perm[j] = perm[p];
+                    perm[p] = t;
+                }
+            }
+        }
+        __syncthreads();
+        const T pivot = colj[j];
+        if (pivot == T(0)) {
+            if (tid == 0 && !fz) fz = j + 1;
+        } else if (cg == 0 && row > j && row < nv) {
+            colj[row] = mx_getrf_scale(colj[row], pivot);
+        }
+        __syncthreads();
+        if (row > j && row < nv) {
+            const T l = colj[row];
+            #pragma unroll 4
+            for (int k = j + 1 + cg; k < nv; k += GETRF_CG) {
+                T* colk = S + k * GETRF_P;
+                colk[row] = mx_getrf_update(colk[row], l, colk[j]);
+            }
+        }
+    }
+    __syncthreads();
+    getrf_block_io<T, 1>(Ajj, lda, S, nv, tid);
+    if (tid < GETRF_W) piv[tid] = o + perm[tid];
+    if (tid == 0 && fz && *first_zero == 0) *first_zero = o + fz;
+}
+
+// Applies the block's permutation to rows [o, o + 128) of the other columns
+// of the image, in place: `rows` is A + o, column cc of the ncols = np - 128
+// handled is image column cc (cc < left_cols = o) or cc + 128. A workgroup
+// owns 128 rows x 8 whole columns: it loads them straight into LDS (a column
+// per half of the workgroup, consecutive lanes down it), and after the
+// barrier stores row g from source row perm[g] - o. Columns are independent
+// and a workgroup holds all 128 rows of its own, so in place is safe.
+template <typename T>
+__global__ void __launch_bounds__(256)
+getrf_rowperm_kernel(T* __restrict__ rows, int64_t lda,
+                     const int* __restrict__ piv, int o, int64_t left_cols,
+                     int64_t ncols) {
+    __shared__ T tile[GETRF_CT * GETRF_W];
+    const int g = threadIdx.x % GETRF_W, h = threadIdx.x / GETRF_W;
+    // a source row is inside the block by construction; the mask keeps a
+    // corrupted entry from reading outside the tile
+    const int src = (piv[g] - o) & (GETRF_W - 1);
+    const int64_t c0 = (int64_t)blockIdx.x * GETRF_CT;
+    #pragma unroll
+    for (int cl = h; cl < GETRF_CT; cl += 2) {
+        const int64_t cc = c0 + cl;
+        if (cc < ncols) {
+            const int64_t col = cc < left_cols ? cc : cc + GETRF_W;
+            tile[g + cl * GETRF_W] = rows[g + col * lda];
+        }
+    }
+    __syncthreads();
+    #pragma unroll
+    for (int cl = h; cl < GETRF_CT; cl += 2) {
+        const int64_t cc = c0 + cl;
+        if (cc < ncols) {
+            const int64_t col = cc < left_cols ? cc : cc + GETRF_W;
+            rows[g + col * lda] = tile[src + cl * GETRF_W];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GEMM launch. Which instantiation a call runs is decided in
 // gemm_launch_policy.h; here are the latched knobs, the record of the last
 // launch, the one step from a selected variant to its compiled kernel, and
@@ -1123,6 +1300,51 @@ int mxk_trsm_diag(int is_fp32, int side, int tt, int rev, int unit, int nv,
         if (side) launch(double{}, trsm_diag_kernel<double, 1>);
         else launch(double{}, trsm_diag_kernel<double, 0>);
     }
+    return (int)hipGetLastError() == 0 ? 0 : -2;
+}
+
+// One diagonal block of the LU factorisation, in place. Ajj is the block's
+// first element (pitch lda), o its offset in the matrix, nv the order left
+// inside it; piv receives the block's 128 entries (global source rows),
+// *first_zero the 1-based global column of a zero pivot if it still holds 0.
+int mxk_getrf_diag(int is_fp32, int nv, int64_t o, void* Ajj, int64_t lda,
+                   int* piv, int* first_zero, hipStream_t stream) {
+    const int64_t e16 = is_fp32 ? 4 : 2;
+    if (is_fp32 & ~1) return -4;
+    if (nv < 1 || nv > GETRF_W || o < 0 || o % GETRF_W) return -4;
+    if (o > INT32_MAX - GETRF_W || !Ajj || !piv || !first_zero) return -4;
+    if (!pitch_ok(lda, GETRF_W, e16)) return -4;
+    if (is_fp32)
+        hipLaunchKernelGGL(getrf_diag_kernel<float>, dim3(1), dim3(GETRF_NT),
+                           0, stream, (float*)Ajj, lda, nv, (int)o, piv,
+                           first_zero);
+    else
+        hipLaunchKernelGGL(getrf_diag_kernel<double>, dim3(1), dim3(GETRF_NT),
+                           0, stream, (double*)Ajj, lda, nv, (int)o, piv,
+                           first_zero);
+    return (int)hipGetLastError() == 0 ? 0 : -2;
+}
+
+// The permutation of block o applied to rows [o, o + 128) of the columns
+// [0, o) and [o + 128, np) of the np x np image A (pitch lda); piv is the
+// block's 128 entries as mxk_getrf_diag wrote them. np == 128 has no other
+// column: nothing is launched.
+int mxk_getrf_rowperm(int is_fp32, int64_t o, int64_t np, void* A,
+                      int64_t lda, const int* piv, hipStream_t stream) {
+    const int64_t e16 = is_fp32 ? 4 : 2;
+    if (is_fp32 & ~1) return -4;
+    if (np < GETRF_W || np % GETRF_W || o < 0 || o % GETRF_W) return -4;
+    if (o > np - GETRF_W || np > INT32_MAX || !A || !piv) return -4;
+    if (!pitch_ok(lda, np, e16)) return -4;
+    const int64_t ncols = np - GETRF_W;
+    if (ncols == 0) return 0;
+    const dim3 grid((unsigned)((ncols + GETRF_CT - 1) / GETRF_CT)), block(256);
+    if (is_fp32)
+        hipLaunchKernelGGL(getrf_rowperm_kernel<float>, grid, block, 0, stream,
+                           (float*)A + o, lda, piv, (int)o, o, ncols);
+    else
+        hipLaunchKernelGGL(getrf_rowperm_kernel<double>, grid, block, 0,
+                           stream, (double*)A + o, lda, piv, (int)o, o, ncols);
     return (int)hipGetLastError() == 0 ? 0 : -2;
 }
 

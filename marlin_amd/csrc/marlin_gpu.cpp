@@ -29,6 +29,7 @@
 #include "gemm_group_plan.h"   // struct mx_dbuf, the grouped-GEMM plan
 #include "gemm_splitk_plan.h"  // the split-K slicing policy
 #include "trsm_plan.h"         // the triangular solve: check and step list
+#include "getrf_plan.h"        // the LU factorisation: check and step list
 #include "aux_guards.h"        // argument checks of the auxiliary entries
 #include "kernels.h"           // the kernels.hip launchers
 
@@ -114,6 +115,10 @@ struct mx_ctx {
   // triangular solve: the -X_j panel (128 * r elements) and the step list
   mx_dbuf wsT;
   mx_trsm_plan trsm_plan;
+  // LU factorisation: the first-zero-pivot word (4 bytes) and the step list;
+  // its -U12 panel is wsT
+  mx_dbuf wsI;
+  mx_getrf_plan getrf_plan;
   mx_stats_t st = {};
 };
 
@@ -181,7 +186,7 @@ int mx_shutdown(mx_ctx* c) {
   if (c->world) ncclCommDestroy(c->world);
   for (mx_dbuf* b : {&c->wsA, &c->wsB, &c->wsC,
                      &c->wsPA[0], &c->wsPA[1], &c->wsPB[0], &c->wsPB[1],
-                     &c->wsG, &c->wsK, &c->wsT})
+                     &c->wsG, &c->wsK, &c->wsT, &c->wsI})
     if (b->ptr) (void)hipFree(b->ptr);
   ctx_teardown(c);
   return MX_OK;
@@ -629,6 +634,67 @@ int mx_trsm_device(mx_ctx* c, int is_fp32, int side, int lower, int trans,
     }
     return 0;
   });
+}
+
+// LU factorisation of a device image (include/marlin_gpu.h). The check and
+// the step list are getrf_plan.h; only a call that passed the whole check
+// allocates or enqueues. Every step is a stream of launches on s_gemm: the
+// diagonal kernel, the row permutation, the two strip solves (the triangular
+// solve's diagonal kernel; T and B are disjoint blocks of the one image,
+// which only the public TRSM entry refuses) and one accumulating GEMM.
+int mx_getrf_device(mx_ctx* c, int is_fp32, int64_t n, mx_dbuf* dA,
+                    int64_t lda, mx_dbuf* dPiv, int* info) {
+  if (!c) return MX_EINVAL;
+  c->st = {};
+  bool empty = false;
+  int rc = mx_getrf_check(128, is_fp32, n, dA, lda, dPiv, info, &empty);
+  if (rc) return rc;
+  *info = 0;
+  c->st.flops = 2.0 * (double)n * (double)n * (double)n / 3.0;
+  if (empty) return MX_OK;
+  mx_getrf_plan& plan = c->getrf_plan;
+  mx_getrf_steps(128, n, lda, &plan);
+  const int64_t elem = is_fp32 ? 4 : 8;
+  HIP_OK(hipSetDevice(c->device));
+  if (plan.ws_elems > INT64_MAX / elem) return MX_ENOMEM;
+  if (plan.ws_elems && (rc = ensure(c, &c->wsT, plan.ws_elems * elem)))
+    return rc;
+  if ((rc = ensure(c, &c->wsI, 4))) return rc;
+  char* ap = (char*)dA->ptr;
+  int* piv = (int*)dPiv->ptr;
+  int* word = (int*)c->wsI.ptr;
+  rc = timed(c, [&] {
+    if (hipMemsetAsync(word, 0, 4, c->s_gemm) != hipSuccess) return -2;
+    for (const mx_getrf_step& st : plan.steps) {
+      int e = mxk_getrf_diag(is_fp32, st.nv, st.o, ap + st.d_off * elem, lda,
+                             piv + st.o, word, c->s_gemm);
+      if (e) return e;
+      e = mxk_getrf_rowperm(is_fp32, st.o, plan.np, ap, lda, piv + st.o,
+                            c->s_gemm);
+      if (e) return e;
+      if (st.rest == 0) continue;
+      // L21 = A21 U11^-1: right, upper, non-unit  (tt = 1, rev = 0)
+      e = mxk_trsm_diag(is_fp32, 1, 1, 0, 0, st.nv, ap + st.d_off * elem, lda,
+                        ap + st.l21_off * elem, lda, c->wsT.ptr, st.rest,
+                        c->s_gemm);
+      if (e) return e;
+      // U12 = L11^-1 (P A12): left, lower, unit  (tt = 0, rev = 0); last,
+      // so that the panel holds -U12
+      e = mxk_trsm_diag(is_fp32, 0, 0, 0, 1, st.nv, ap + st.d_off * elem, lda,
+                        ap + st.u12_off * elem, lda, c->wsT.ptr, st.rest,
+                        c->s_gemm);
+      if (e) return e;
+      e = mxk_gemm_op(is_fp32, 1, 0, 0, st.rest, st.rest, 128,
+                      ap + st.l21_off * elem, lda, c->wsT.ptr, plan.ws_pitch,
+                      ap + st.a22_off * elem, lda, c->s_gemm);
+      if (e) return e;
+      c->st.gemm_launches += 1;
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  HIP_OK(hipMemcpy(info, word, 4, hipMemcpyDeviceToHost));
+  return MX_OK;
 }
 
 // The mx_last_gemm_* entries: views of the one record kernels.hip keeps.

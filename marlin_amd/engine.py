@@ -161,6 +161,8 @@ def _load():
         "mx_last_gemm_splitk": (ctypes.c_int, [vp, P(ctypes.c_int), P(i64)]),
         "mx_trsm_device": (ctypes.c_int, [vp] + [ctypes.c_int] * 5
                            + [i64, i64, vp, i64, vp, i64]),
+        "mx_getrf_device": (ctypes.c_int, [vp, ctypes.c_int, i64, vp, i64, vp,
+                                           P(ctypes.c_int)]),
         "mx_map_device": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, i64,
                                          vp, vp, dbl, vp]),
     }
@@ -707,6 +709,41 @@ class Engine:
         self.trsm_raw(n, r, T.buf, T.pitch, B.buf, B.pitch, s, lower, trans,
                       unit_diag, T.fp32)
         return B
+
+    def getrf_raw(self, n, dA, lda, dPiv, fp32=False, check=True):
+        """mx_getrf_device on raw device buffers: the order-n matrix in the
+        np x np image dA (np = n rounded up to 128, pitch lda in elements,
+        zero pads) becomes packed L\\U in place, dPiv (np int32) its row
+        permutation. Returns (rc, info): the entry's code, and 0 or the
+        1-based column of the first zero pivot; info is None where the
+        entry refused the call. check=True raises on a non-zero code."""
+        info = ctypes.c_int(-1)
+        rc = lib().mx_getrf_device(self._ctx, int(fp32), n, dA, lda, dPiv,
+                                   ctypes.byref(info))
+        if check:
+            _ck(rc, "mx_getrf_device")
+        return rc, (info.value if rc == 0 else None)
+
+    def getrf_dd(self, A):
+        """LU factorisation of a square cached matrix, in place: A's image
+        becomes packed L\\U (unit-lower L, upper U), pivoting inside each
+        128 x 128 diagonal block. Returns (p_array, info): p_array an int64
+        array of n with A_before[p_array] == L @ U, info as getrf_raw."""
+        n = A.m
+        if A.n != n:
+            raise ValueError(
+                f"LU decompose only support square matrix: {A.m} v.s {A.n}")
+        if n == 0:
+            return np.zeros(0, dtype=np.int64), 0
+        npad = (n + 127) // 128 * 128
+        piv = np.empty(npad, dtype=np.int32)
+        d_piv = self.alloc(piv.nbytes)
+        try:
+            _, info = self.getrf_raw(n, A.buf, A.pitch, d_piv, A.fp32)
+            self.download(piv, d_piv, piv.nbytes)
+        finally:
+            self.free(d_piv)
+        return piv[:n].astype(np.int64), info
 
     def map_raw(self, op, n, dA, dB, scalar, dC, fp32=False, check=True):
         """mx_map_device on raw device buffers: the elementwise op (a name

@@ -12,7 +12,9 @@
 # PCIe; sign flips are folded into the small host factors so no device
 # elementwise pass is needed. cholesky_decompose(panel="trsm") and lu_solve
 # instead use the device triangular solve (Engine.trsm_raw / trsm_dd): no
-# inverse is formed and the factor is uploaded once.
+# inverse is formed and the factor is uploaded once. lu_factor_device goes
+# further: the whole LU runs on the device (Engine.getrf_dd, pivoting inside
+# 128-wide diagonal blocks) and the factor stays there for its solves.
 #
 # luDecompose: block pairwise pivoting (pivoting INSIDE each diagonal
 # block only — the reference's scheme). Returns (blocks, p_array) with
@@ -51,13 +53,109 @@ def _gemm_batch(eng, problems, grouped, **kw):
     return [eng.gemm_dd(A, B, C, **kw) for A, B, C in problems]
 
 
-def lu_decompose(dvm, mode="auto", base_size=1000, grouped=True):
+class DeviceLU:
+    """The packed L\\U factor of a square matrix, resident on the device,
+    with its row permutation (A[p_array] == L @ U). Made by
+    lu_factor_device; reusable for any number of solves; owns its image
+    until free() (also the end of a `with` block)."""
+
+    def __init__(self, eng, image, p_array):
+        self._eng, self._image = eng, image
+        self.p_array = p_array
+        self.n = image.m
+        self.fp32 = image.fp32
+
+    def solve(self, rhs):
+        """x with A x = rhs, a vector of n or an n x c matrix (its columns
+        are padded to 128 on the device); the result has its shape and the
+        factor's element type. The right-hand side is permuted on the host
+        and uploaded; the factor is read where it lies, as unit-lower L and
+        then as upper U (Engine.trsm_dd)."""
+        if self._image is None:
+            raise ValueError("DeviceLU used after free()")
+        dt = np.float32 if self.fp32 else np.float64
+        b = np.asarray(rhs, dtype=dt)
+        if b.ndim not in (1, 2) or b.shape[0] != self.n:
+            raise ValueError(
+                f"right-hand side must have {self.n} rows: {b.shape}")
+        pb = b.reshape(self.n, -1)[self.p_array, :]   # (P b)[g] = b[p[g]]
+        d_b = self._eng.upload_matrix(pb, fp32=self.fp32)
+        try:
+            self._eng.trsm_dd(self._image, d_b, side="left", lower=True,
+                              unit_diag=True)
+            self._eng.trsm_dd(self._image, d_b, side="left", lower=False)
+            x = self._eng.download_matrix(d_b)
+        finally:
+            d_b.free()
+        return x[:, 0] if b.ndim == 1 else x
+
+    def download(self):
+        """(packed L\\U as an n x n ndarray, p_array)."""
+        if self._image is None:
+            raise ValueError("DeviceLU used after free()")
+        return self._eng.download_matrix(self._image), self.p_array
+
+    def free(self):
+        """Releases the device image; a second call is a no-op."""
+        if self._image is not None:
+            self._image.free()
+            self._image = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+def lu_factor_device(dvm, fp32=False):
+    """LU of a square DenseVecMatrix wholly on the device: one upload, then
+    Engine.getrf_dd (mx_getrf_device: a stream of launches, pivoting inside
+    each 128 x 128 diagonal block, no host step). Returns a DeviceLU that
+    keeps the packed factor on the device. Raises np.linalg.LinAlgError
+    naming the column when a pivot is exactly zero. A matrix that needs a
+    pivot from another block row is outside what block-local pivoting
+    covers, here at width 128 as in lu_decompose at base_size."""
+    a = dvm.toBreeze()
+    if a.shape[0] != a.shape[1]:
+        raise ValueError(
+            f"LU decompose only support square matrix: {a.shape[0]} v.s "
+            f"{a.shape[1]}")
+    eng = dvm._engine()
+    image = eng.upload_matrix(a, fp32=fp32)
+    try:
+        p_array, info = eng.getrf_dd(image)
+        if info:
+            raise np.linalg.LinAlgError(
+                f"zero pivot in column {info} (1-based) of the block-pivoted "
+                f"LU: U is singular")
+    except BaseException:
+        image.free()
+        raise
+    return DeviceLU(eng, image, p_array)
+
+
+def lu_decompose(dvm, mode="auto", base_size=1000, grouped=True,
+                 panel="host"):
     """DenseVecMatrix.luDecompose (DenseVecMatrix.scala:283-464).
     Returns (BlockMatrix with packed L\\U, p_array) where p_array[g] is
-    the source row of output row g within its block row."""
+    the source row of output row g within its block row.
+    panel="host" (the default) factors each diagonal base block on the
+    host. panel="device" returns the same contract from
+    lu_factor_device(dvm).download(): the whole factorisation runs on the
+    device with pivoting inside 128-wide diagonal blocks, and mode,
+    base_size and grouped play no part."""
     from .api import BlockMatrix
     import scipy.linalg
 
+    if panel not in ("host", "device"):
+        raise ValueError(f"panel must be 'host' or 'device': {panel!r}")
+    if panel == "device":
+        with lu_factor_device(dvm) as f:
+            lu, p_array = f.download()
+        n = lu.shape[0]
+        return (BlockMatrix({(0, 0): lu}, n, n, engine=dvm._eng), p_array)
     a = dvm.toBreeze()
     n = a.shape[0]
     if a.shape[0] != a.shape[1]:
