@@ -421,7 +421,9 @@ int mx_last_gemm_splitk(mx_ctx* ctx, int* slices, int64_t* workspace_bytes);
  * side sweeps the blocks forward when eff_lower and the right side when
  * !eff_lower, otherwise backward. Step j (a) solves diagonal block j against
  * all r right-hand sides with the diagonal kernel, substitution in
- * ascending order of the eliminated index, which writes X_j into B and -X_j
+ * ascending order of the eliminated index, each update one fused
+ * multiply-add and each quotient one division in both element types
+ * (trsm_plan.h, mx_trsm_update and mx_trsm_quot), which writes X_j into B and -X_j
  * into a workspace panel of 128 * r elements the context owns (grown on
  * demand, freed by mx_shutdown), then (b) accumulates into ALL remaining
  * blocks with one launch of the plain GEMM (beta_one = 1, k = 128):

@@ -846,7 +846,10 @@ splitk_reduce_kernel(T* __restrict__ C, int64_t ldc, int64_t m, int64_t n,
 //     Every lane runs the same forward substitution on a lower-triangular
 //     L, y_a = (v_a - sum_{b<a} L[a][b] y_b) / L[a][a], subtracting in
 //     ascending b: the order of a result's operations is fixed by the code
-//     alone, no atomics, no cross-lane sums. Side, triangle, transpose and
+//     alone, no atomics, no cross-lane sums, and each operation is one of
+//     trsm_plan.h's two (mx_trsm_update, one fused multiply-add, and
+//     mx_trsm_quot, one division), so neither is the rounding left to the
+//     compiler's contraction. Side, triangle, transpose and
 //     unit diagonal are resolved when L is staged (mx_trsm_stage: transpose
 //     on load, reversal of the index for an upper form, 1 on a unit
 //     diagonal, the identity at an index >= nv), element by element, so
@@ -972,20 +975,28 @@ trsm_diag_kernel(const T* __restrict__ Tjj, int64_t ldt, T* __restrict__ X,
         #pragma unroll
         for (int i = 0; i < TRSM_PB; i++)
             y[i] = tile[(a0 + i) * TRSM_TP + lane];
+        // the divisors of this panel, loaded ahead of the loop below so
+        // that none is fetched between two dependent divisions
+        T dg[TRSM_PB];
+        #pragma unroll
+        for (int i = 0; i < TRSM_PB; i++)
+            dg[i] = Lp[(a0 + i) * TRSM_PB + i];
         // the rows solved by earlier panels
         for (int b = 0; b < a0; b++) {
             const T yb = tile[b * TRSM_TP + lane];
             const T* col = Lp + b * TRSM_PB;
             #pragma unroll
-            for (int i = 0; i < TRSM_PB; i++) y[i] -= col[i] * yb;
+            for (int i = 0; i < TRSM_PB; i++)
+                y[i] = mx_trsm_update(y[i], col[i], yb);
         }
         // the triangle of this panel, in registers
         #pragma unroll
         for (int i = 0; i < TRSM_PB; i++) {
             const T* col = Lp + (a0 + i) * TRSM_PB;
-            y[i] = y[i] / col[i];
+            y[i] = mx_trsm_quot(y[i], dg[i]);
             #pragma unroll
-            for (int i2 = i + 1; i2 < TRSM_PB; i2++) y[i2] -= col[i2] * y[i];
+            for (int i2 = i + 1; i2 < TRSM_PB; i2++)
+                y[i2] = mx_trsm_update(y[i2], col[i2], y[i]);
         }
         #pragma unroll
         for (int i = 0; i < TRSM_PB; i++)

@@ -1,9 +1,11 @@
 // trsm_plan.h — host-only integer code of the triangular solve entry
 // (mx_trsm_device): the argument check, the list of steps of the blocked
-// sweep, and the one statement of how a diagonal block is staged. No HIP
-// here, so a plain CPU program can check it (tests/test_trsm_plan.py builds
-// one under AddressSanitizer + UBSan and runs the plan at a small block
-// width against direct substitution).
+// sweep, and the one statement of how a diagonal block is staged and of the
+// element operations of its substitution. No HIP here, so a plain CPU
+// program can check it (tests/test_trsm_plan.py builds one under
+// AddressSanitizer + UBSan and runs the plan at a small block width against
+// direct substitution; tests/test_diag_bits_cpu.py runs the substitution
+// at the device's width on rounding data).
 //
 // The sweep (include/marlin_gpu.h states the contract for callers). T is
 // cut into w x w blocks, w = 128 on the device. With eff_lower = lower XOR
@@ -62,7 +64,44 @@ TRSM_FN int mx_trsm_stage(int w, int tt, int rev, int unit, int nv, int a,
   return load ? MX_TRSM_LOAD : a == b ? MX_TRSM_ONE : MX_TRSM_ZERO;
 }
 
+// ---------------------------------------------------------------------------
+// The element operations of the substitution (shared with the kernel, which
+// performs exactly these on each element, in ascending b).
+//
+// The update acc -= l * y is ONE fused multiply-add, fma(-l, y, acc): a
+// single rounding, in the kernel and on the host alike. Written as
+// acc - l * y it would be left to the compiler's contraction, which fuses
+// some of a kernel's updates and splits others into a multiply and a
+// subtract (two roundings), differently from one compiler to the next.
+TRSM_FN double mx_trsm_update(double acc, double l, double y) {
+  return __builtin_fma(-l, y, acc);
+}
+TRSM_FN float mx_trsm_update(float acc, float l, float y) {
+  return __builtin_fmaf(-l, y, acc);
+}
+
+// The quotient y = acc / d: one division, not a multiplication by a
+// reciprocal.
+TRSM_FN double mx_trsm_quot(double acc, double d) { return acc / d; }
+TRSM_FN float mx_trsm_quot(float acc, float d) { return acc / d; }
+
 #ifdef MX_TRSM_HOST
+// ---------------------------------------------------------------------------
+// The substitution on one right-hand side, in place: L is the staged w x w
+// lower-triangular matrix, L[a * w + b] its element (a, b); v holds the
+// right-hand side in canonical order on entry and y on return. Element a
+// takes its updates in ascending b and then its one division, which is what
+// the kernel does to it (there the loop runs the other way round, column b
+// into every later row, and an element sees the same sequence).
+template <typename T>
+static inline void mx_trsm_substitute(int w, const T* L, T* v) {
+  for (int a = 0; a < w; a++) {
+    T acc = v[a];
+    for (int b = 0; b < a; b++) acc = mx_trsm_update(acc, L[a * w + b], v[b]);
+    v[a] = mx_trsm_quot(acc, L[a * w + a]);
+  }
+}
+
 // ---------------------------------------------------------------------------
 struct mx_trsm_step {
   int64_t j0;                 // first index of diagonal block j

@@ -88,6 +88,105 @@ def block_lu(a, w=W, tie_cols=None):
     return a, piv, info
 
 
+# ---------------------------------------------------------------------------
+# the diagonal kernel's arithmetic, restated (test_gpu_diag_bits.py compares
+# the device with it bit for bit on rounding data; test_diag_bits_cpu.py
+# proves it against mx_getrf_eliminate of marlin_amd/csrc/getrf_plan.h)
+MODELS = ("fused", "unfused", "reciprocal")
+
+
+def eliminate_restated(block, nv, model="fused"):
+    """(block after, perm, first_zero) of mx_getrf_eliminate on the leading
+    nv x nv part of a square block, in its element type: column by column,
+    the pivot by block_lu's key rule (largest |a|, a NaN counts as -1, the
+    first of equal keys), the multiplier l = a / pivot (one division), the
+    update fma(-l, u, a) (one rounding) over the whole trailing block at
+    once. perm[g] is the source row of output row g, first_zero the 1-based
+    column of the first exactly-zero pivot or 0. `model` degrades it on
+    purpose: "unfused" rounds the product before the subtraction,
+    "reciprocal" multiplies by 1 / pivot."""
+    import _fma
+    assert model in MODELS
+    a = np.array(block, order="F", copy=True)
+    dt = a.dtype.type
+    perm = np.arange(a.shape[0])
+    first_zero = 0
+    with np.errstate(all="ignore"):
+        for j in range(nv):
+            col = a[j:nv, j]
+            key = np.where(np.isnan(col), -1, np.abs(col))
+            p = j + int(np.argmax(key))          # the first of the maxima
+            if p != j:
+                a[[j, p], :nv] = a[[p, j], :nv]
+                perm[[j, p]] = perm[[p, j]]
+            d = a[j, j]
+            if d == 0:
+                first_zero = first_zero or j + 1
+            elif model == "reciprocal":
+                a[j + 1:nv, j] = a[j + 1:nv, j] * (dt(1) / d)
+            else:
+                a[j + 1:nv, j] = a[j + 1:nv, j] / d
+            l, u = a[j + 1:nv, j][:, None], a[j, j + 1:nv][None, :]
+            if dt is np.float64:
+                assert _fma.in_range64(l[np.isfinite(l)], u[np.isfinite(u)]), \
+                    "outside the range fma64 is valid in"
+            if model == "unfused":
+                a[j + 1:nv, j + 1:nv] = a[j + 1:nv, j + 1:nv] - l * u
+            else:
+                a[j + 1:nv, j + 1:nv] = _fma.fma(-l, u, a[j + 1:nv, j + 1:nv])
+    return a, perm, first_zero
+
+
+def same_bits(got, want):
+    """Bit for bit after -0 -> +0, a NaN matching any NaN: the comparison
+    of the rounding-data tests. Returns the (row, col) of the mismatches."""
+    U = UINT[got.dtype.type]
+    g, w = zero_sign_dropped(got), zero_sign_dropped(want)
+    gn, wn = np.isnan(g), np.isnan(w)
+    return np.argwhere((gn != wn) | (~gn & (g.view(U) != w.view(U))))
+
+
+@functools.lru_cache(maxsize=None)
+def normal_problem(fp32, n, scale_exp=0):
+    """A n x n in the element type: standard normal, nothing dominant, times
+    2^scale_exp (exact but where it leaves the normal range, which is the
+    point of scale_exp = -130 in fp32: entries, updates and results are
+    subnormal there, the multipliers stay O(1))."""
+    dt = dtype_of(fp32)
+    rng = np.random.RandomState(_seed(5, fp32, n))
+    a = rng.standard_normal((n, n)).astype(dt)
+    a = np.ldexp(a, scale_exp).astype(dt)
+    return _frozen(np.asfortranarray(a))[0]
+
+
+NAN_N = 128
+
+
+@functools.lru_cache(maxsize=None)
+def nan_problem(fp32):
+    """(A, r): normal_problem at n = 128 with one NaN in column 0 at a row r
+    that is not column 0's pivot row. The NaN is never chosen while another
+    entry remains: row r turns NaN whole at step 0 (its multiplier is NaN),
+    is passed over at every later column and ends at the bottom, and no
+    other row ever meets it."""
+    a = np.array(normal_problem(fp32, NAN_N))
+    r = 5 if int(np.argmax(np.abs(a[:, 0]))) != 5 else 6
+    a[r, 0] = np.nan
+    return _frozen(a)[0], r
+
+
+@functools.lru_cache(maxsize=None)
+def inf_problem(fp32):
+    """(A, r1, r2): normal_problem at n = 128 with +inf at (r1, 0) and -inf
+    at (r2, 0), r1 < r2: two candidates of equal key, the lowest row wins.
+    Row r2's multiplier is -inf / inf = NaN, so it goes the way of
+    nan_problem's row; every other multiplier of column 0 is a zero."""
+    a = np.array(normal_problem(fp32, NAN_N))
+    r1, r2 = 40, 90
+    a[r1, 0], a[r2, 0] = np.inf, -np.inf
+    return _frozen(a)[0], r1, r2
+
+
 def block_lu_solve(a, b, w=W):
     """x with a x = b through block_lu and two substitutions, everything in
     a's element type: the host solve the device one is compared with."""

@@ -1,7 +1,10 @@
 # Shapes, inputs and device runs of the triangular-solve tests
 # (test_gpu_trsm.py, test_gpu_trsm_consumers.py) and the Python restatement
 # of the entry's argument check that test_trsm_plan.py compares with the
-# C++ (marlin_amd/csrc/trsm_plan.h). No GPU is needed to import this.
+# C++ (marlin_amd/csrc/trsm_plan.h), and the numpy restatement of the
+# diagonal kernel's arithmetic (stage_restated, substitute_restated) that
+# test_gpu_diag_bits.py compares the device with on rounding data. No GPU is
+# needed to import this.
 #
 # Exact data: X is integer in [-8, 8]; T has off-diagonal integers in
 # [-2, 2] and a diagonal from {+-1/2, +-1, +-2, +-4} (1 when unit_diag);
@@ -238,6 +241,89 @@ def run_exact(eng, fp32, form, n, r):
         t_untouched=bool((tafter.view(U) == timg.view(U)).all()),
         flops=st["flops"], launches=st["gemm_launches"])
     return rec
+
+
+# ---------------------------------------------------------------------------
+# the diagonal kernel's arithmetic, restated (test_gpu_diag_bits.py compares
+# the device with it bit for bit; test_diag_bits_cpu.py proves it against
+# the C++ of marlin_amd/csrc/trsm_plan.h)
+def stage_restated(form, t, nv):
+    """(L, orig): mx_trsm_stage and mx_trsm_orig in Python. L is the staged
+    128 x 128 lower-triangular matrix of the diagonal block t (128 x 128 as
+    stored, whatever lies outside the referenced part): the transpose
+    resolved, an upper form reversed, 1 on a unit diagonal, the identity at
+    an original index >= nv. orig[a] is the original index of canonical a."""
+    side, lower, trans, unit = form
+    tt = trans ^ side
+    rev = 0 if (lower ^ tt) else 1
+    orig = (W - 1 - np.arange(W)) if rev else np.arange(W)
+    a, b = np.indices((W, W))
+    oa, ob = orig[a], orig[b]
+    inside = (a >= b) & (oa < nv) & (ob < nv)
+    load = inside & ~((a == b) & bool(unit))
+    src = t[ob, oa] if tt else t[oa, ob]
+    L = np.where(load, src, (a == b).astype(t.dtype)).astype(t.dtype)
+    return L, orig
+
+
+def block_images(fp32, form, n, r=W):
+    """(T image, B image) of a one-block case (n <= 128) on rounding data:
+    rounding_problem on poisoned images with padded pitches."""
+    side, lower, trans, unit = form
+    dt = dtype_of(fp32)
+    t, b = rounding_problem(fp32, side, lower, trans, n, r)
+    return (t_image(t, lower, unit, W + PAD, dt),
+            b_image(b, side, n, r, (r if side else W) + PAD, dt))
+
+
+def block_of_images(form, timg, bimg, r=W):
+    """(the 128 x 128 diagonal block as stored, the strip) inside them."""
+    strip = bimg[:r, :W] if form[0] else bimg[:W, :r]
+    return np.asfortranarray(timg[:W, :W]), np.asfortranarray(strip)
+
+
+MODELS = ("fused", "unfused", "reciprocal", "reversed")
+
+
+def substitute_restated(form, t, b, nv, model="fused"):
+    """What trsm_diag_kernel leaves in the strip b (128 x r on the left,
+    r x 128 on the right) for the diagonal block t, in t's element type.
+    Right-looking, b ascending: y_b = mx_trsm_quot(acc_b, L[b][b]), then
+    acc_a = mx_trsm_update(acc_a, L[a][b], y_b) = fma(-L[a][b], y_b, acc_a)
+    for every a > b at once: an element sees its updates in ascending b,
+    the kernel's order. `model` degrades it on purpose, for the tests that
+    show such a kernel would be told apart: "unfused" rounds the product
+    before the subtraction, "reciprocal" multiplies by 1 / L[b][b],
+    "reversed" gives each element its updates in descending b."""
+    import _fma
+    assert model in MODELS
+    side = form[0]
+    dt = t.dtype.type
+    L, orig = stage_restated(form, np.asarray(t), nv)
+    acc = np.array(b.T[orig, :] if side else b[orig, :], dtype=dt, order="C")
+    with np.errstate(all="ignore"):
+        if model == "reversed":
+            for a in range(W):
+                for c in range(a - 1, -1, -1):
+                    acc[a] = _fma.fma(-L[a, c], acc[c], acc[a])
+                acc[a] = acc[a] / L[a, a]
+        else:
+            for c in range(W):
+                if model == "reciprocal":
+                    acc[c] = acc[c] * (dt(1) / L[c, c])
+                else:
+                    acc[c] = acc[c] / L[c, c]
+                l, y = L[c + 1:, c][:, None], acc[c][None, :]
+                if dt is np.float64:
+                    assert _fma.in_range64(l, y, addend=acc[c + 1:]), \
+                        "outside the range fma64 is valid in"
+                if model == "unfused":
+                    acc[c + 1:] = acc[c + 1:] - l * y
+                else:
+                    acc[c + 1:] = _fma.fma(-l, y, acc[c + 1:])
+    out = np.empty_like(acc)
+    out[orig, :] = acc
+    return np.asfortranarray(out.T if side else out)
 
 
 def residual_ratio(fp32, form, t, b, x):

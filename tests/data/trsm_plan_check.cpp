@@ -197,25 +197,29 @@ static double opT(const std::vector<double>& full, int64_t n, int trans,
 static void diag_solve(int side, const mx_trsm_plan& p, const mx_trsm_step& st,
                        int unit, image& T, image& B, std::vector<double>& ws,
                        int64_t r) {
-  double L[W][W];
+  double L[W * W];
   for (int a = 0; a < W; a++)
     for (int b = 0; b < W; b++) {
       int64_t off = 0;
       const int kind = mx_trsm_stage(W, p.tt, p.rev, unit, st.nv, a, b, T.ld,
                                      &off);
-      L[a][b] = kind == MX_TRSM_LOAD ? T.mem.at((size_t)(st.t_off + off))
-                                     : (double)kind;
+      L[a * W + b] = kind == MX_TRSM_LOAD ? T.mem.at((size_t)(st.t_off + off))
+                                          : (double)kind;
     }
   for (int64_t c = 0; c < r; c++) {
     double y[W];
+    double* x[W];
     for (int a = 0; a < W; a++) {
       const int oa = mx_trsm_orig(W, p.rev, a);
-      double* x = side ? &B.mem.at((size_t)(st.x_off + c + oa * B.ld))
-                       : &B.mem.at((size_t)(st.x_off + oa + c * B.ld));
-      double v = *x;
-      for (int b = 0; b < a; b++) v -= L[a][b] * y[b];
-      y[a] = v / L[a][a];
-      *x = y[a];
+      x[a] = side ? &B.mem.at((size_t)(st.x_off + c + oa * B.ld))
+                  : &B.mem.at((size_t)(st.x_off + oa + c * B.ld));
+      y[a] = *x[a];
+    }
+    // the header's substitution: mx_trsm_update in ascending b, mx_trsm_quot
+    mx_trsm_substitute(W, L, y);
+    for (int a = 0; a < W; a++) {
+      const int oa = mx_trsm_orig(W, p.rev, a);
+      *x[a] = y[a];
       ws.at((size_t)(side ? c + oa * r : oa + c * W)) = -y[a];
     }
   }

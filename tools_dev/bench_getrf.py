@@ -3,14 +3,16 @@
 #
 #   python tools_dev/bench_getrf.py [--mode entry|lu|solve|all] [--reps 3]
 #       [--out F] [--entry-n 1024,4096,8000] [--n 8000] [--base 1000]
+#       [--fp32]
 #
 # One process; the arms of a comparison alternate run by run so all see the
 # same device state; one warm-up per arm, then --reps repetitions. wall_ms
 # is the host clock around calls that end in a device synchronise, dev_ms
 # the entry's own hipEvent time (mx_stats gemm_ms). One JSON line per
 # compared point, the lists in run order with the warm-up first.
-#   entry  mx_getrf_device, fp64, on a freshly uploaded resident image
-#          (the upload is outside the clock), at each --entry-n.
+#   entry  mx_getrf_device, fp64 (fp32 with --fp32), on a freshly uploaded
+#          resident image (the upload is outside the clock), at each
+#          --entry-n.
 #   lu     lu_decompose(mode="dist", base_size=--base) at --n, panel="device"
 #          against panel="host", host matrix in, host factor out.
 #   solve  DenseVecMatrix.solve at --n, one right-hand side: factor="device"
@@ -49,18 +51,19 @@ def dominant(n, seed):
     return np.asfortranarray(rng.uniform(0, 1, size=(n, n)) + n * np.eye(n))
 
 
-def bench_entry(eng, outf, n, reps):
+def bench_entry(eng, outf, n, reps, fp32=False):
     a = dominant(n, 1)
     npad = (n + 127) // 128 * 128
     d_piv = eng.alloc(npad * 4)
-    rec = {"bench": "entry", "n": n, "fp64": True, "flops": 2.0 * n ** 3 / 3,
+    rec = {"bench": "entry", "n": n, "fp64": not fp32,
+           "flops": 2.0 * n ** 3 / 3,
            "getrf": {"wall_ms": [], "dev_ms": [], "info": []}}
     try:
         for it in range(reps + 1):
-            dA = eng.upload_matrix(a)
+            dA = eng.upload_matrix(a, fp32)
             try:
                 w, (_, info) = timed(lambda: eng.getrf_raw(n, dA.buf, dA.pitch,
-                                                           d_piv))
+                                                           d_piv, fp32))
                 rec["getrf"]["wall_ms"].append(w)
                 rec["getrf"]["dev_ms"].append(eng.stats()["gemm_ms"])
                 rec["getrf"]["info"].append(info)
@@ -153,6 +156,8 @@ def main():
     ap.add_argument("--entry-n", default="1024,4096,8000")
     ap.add_argument("--n", type=int, default=8000)
     ap.add_argument("--base", type=int, default=1000)
+    ap.add_argument("--fp32", action="store_true",
+                    help="the entry mode in fp32")
     args = ap.parse_args()
     from marlin_amd import Engine
     eng = Engine(0)
@@ -160,7 +165,7 @@ def main():
     try:
         if args.mode in ("entry", "all"):
             for n in (int(v) for v in args.entry_n.split(",")):
-                bench_entry(eng, outf, n, max(args.reps, 5))
+                bench_entry(eng, outf, n, max(args.reps, 5), args.fp32)
         if args.mode in ("lu", "all"):
             bench_lu(eng, outf, args.n, args.base, args.reps)
         if args.mode in ("solve", "all"):

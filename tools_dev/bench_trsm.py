@@ -3,15 +3,15 @@
 #
 #   python tools_dev/bench_trsm.py [--mode entry|cholesky|solve|all]
 #       [--reps 5] [--out F] [--n 1024] [--r 11264] [--chol-n 12000]
-#       [--solve-n 8000] [--base 1000]
+#       [--solve-n 8000] [--base 1000] [--fp32]
 #
 # One process; the two arms of a comparison alternate run by run so both
 # see the same device state; one warm-up per arm, then --reps repetitions.
 # wall_ms is the host clock around calls that end in a device synchronise,
 # dev_ms the entry's own hipEvent time (mx_stats gemm_ms). One JSON line
 # per compared point, the lists in run order with the warm-up first.
-#   entry     mx_trsm_device, fp64, n x r, left-lower-unit and right-upper,
-#             operands resident. The other arm is the panel scale as
+#   entry     mx_trsm_device, fp64 (fp32 with --fp32), n x r,
+#             left-lower-unit and right-upper, operands resident. The other arm is the panel scale as
 #             lu_decompose does it for the same panel: inverse of the
 #             n x n block on the host, upload of the factor (and, on the
 #             left, of its negation: the U12 panel and the -L^-1 A12 panel
@@ -49,7 +49,7 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def bench_entry(eng, outf, n, r, reps):
+def bench_entry(eng, outf, n, r, reps, fp32=False):
     assert n % 128 == 0 and r % n == 0
     rng = np.random.RandomState(1)
     nblk = r // n
@@ -59,20 +59,22 @@ def bench_entry(eng, outf, n, r, reps):
         # timed loop does) keeps B finite
         t = rng.uniform(-1, 1, size=(n, n)) / n
         t = np.tril(t, -1) + np.eye(n) if lower else np.triu(t, 1) + 2 * np.eye(n)
-        dT = eng.upload_matrix(t)
+        dT = eng.upload_matrix(t, fp32)
         shape = (r, n) if side else (n, r)
-        dB = eng.upload_matrix(rng.uniform(-1, 1, size=shape))
+        dB = eng.upload_matrix(rng.uniform(-1, 1, size=shape), fp32)
         ldb = dB.pitch
         # the other arm's operands: the panel as nblk blocks of n x n
-        blocks = [eng.upload_matrix(rng.uniform(-1, 1, size=(n, n)))
+        blocks = [eng.upload_matrix(rng.uniform(-1, 1, size=(n, n)), fp32)
                   for _ in range(nblk)]
-        rec = {"bench": "entry", "form": name, "n": n, "r": r, "fp64": True,
+        rec = {"bench": "entry", "form": name, "n": n, "r": r,
+               "fp64": not fp32,
                "trsm": {"wall_ms": [], "dev_ms": []},
                "inverse_gemm": {"wall_ms": [], "host_ms": [], "upload_ms": [],
                                 "gemm_wall_ms": [], "dev_ms": []}}
         for _ in range(reps + 1):
             w, _ = timed(lambda: eng.trsm_raw(n, r, dT.buf, dT.pitch, dB.buf,
-                                              ldb, side, lower, 0, unit))
+                                              ldb, side, lower, 0, unit,
+                                              fp32))
             rec["trsm"]["wall_ms"].append(w)
             rec["trsm"]["dev_ms"].append(eng.stats()["gemm_ms"])
 
@@ -80,11 +82,11 @@ def bench_entry(eng, outf, n, r, reps):
                 h, inv = timed(lambda: np.linalg.solve(t, np.eye(n)) if lower
                                else np.linalg.inv(t))
                 if side:
-                    u, ups = timed(lambda: [eng.upload_matrix(inv)])
+                    u, ups = timed(lambda: [eng.upload_matrix(inv, fp32)])
                     probs = [(blk, ups[0], None) for blk in blocks]
                 else:
-                    u, ups = timed(lambda: [eng.upload_matrix(inv),
-                                            eng.upload_matrix(-inv)])
+                    u, ups = timed(lambda: [eng.upload_matrix(inv, fp32),
+                                            eng.upload_matrix(-inv, fp32)])
                     probs = ([(ups[1], blk, None) for blk in blocks]
                              + [(ups[0], blk, None) for blk in blocks])
                 g, done = timed(lambda: eng.gemm_grouped(probs))
@@ -176,13 +178,15 @@ def main():
     ap.add_argument("--chol-n", type=int, default=12000)
     ap.add_argument("--solve-n", type=int, default=8000)
     ap.add_argument("--base", type=int, default=1000)
+    ap.add_argument("--fp32", action="store_true",
+                    help="the entry mode in fp32")
     args = ap.parse_args()
     from marlin_amd import Engine
     eng = Engine(0)
     outf = open(args.out, "a") if args.out else None
     try:
         if args.mode in ("entry", "all"):
-            bench_entry(eng, outf, args.n, args.r, args.reps)
+            bench_entry(eng, outf, args.n, args.r, args.reps, args.fp32)
         if args.mode in ("cholesky", "all"):
             bench_cholesky(eng, outf, args.chol_n, args.base,
                            min(args.reps, 3))
